@@ -10,8 +10,15 @@ host memory (ingest, DWT, quantiser, tier-1, PCRD, tier-2) for every image of
 the batch; value = megapixels of every image encoded / timed seconds.  Images are independent, so N GPUs run N replicas (weak scaling,
 no collective on the data path); the barrier/max are only for timing.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (driver, N > 1)
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes the files of the last timed step (dump_outputs
+below).  Everything else the bench measures or checks -- single-image latency,
+the PCIe-inclusive leg, rooflines, validation against the oracle's hashes and a
+decoder, the lossless C3/C4 legs, the file-to-file spans, C5 and the CPU
+baselines -- runs only with --full.
 """
 from __future__ import annotations
 
@@ -370,6 +377,35 @@ def sq_counters(kernel):
     return keep
 
 
+DUMP_SEED = 20260119
+DUMP_FLOATS = 1 << 23  # float32 values of the byte sample, all files together (32 MiB)
+
+
+def dump_outputs(dirname, files, prefix=""):
+    """--dump-outputs: what the timed path handed its caller in the last timed
+    step -- one JPX file per image of the step, in step order (objects with
+    view() and close(); closed here).  The files of a step are 9 MB each, so
+    per file: its length and the sum of its bytes (float64, exact) and the
+    bytes at fixed seeded positions floor(u * length), u uniform in [0, 1) and
+    sorted (float32); the same u for every file and every run.
+      jpx_len.npy [n]   jpx_bytesum.npy [n]   jpx_sample.npy [n, k]"""
+    os.makedirs(dirname, exist_ok=True)
+    k = max(1, min(1 << 19, DUMP_FLOATS // max(1, len(files))))
+    u = np.sort(np.random.default_rng(DUMP_SEED).random(k))
+    lens = np.zeros(len(files), np.float64)
+    sums = np.zeros(len(files), np.float64)
+    sample = np.zeros((len(files), k), np.float32)
+    for i, f in enumerate(files):
+        a = np.frombuffer(f.view(), np.uint8)
+        lens[i] = a.size
+        sums[i] = float(a.sum(dtype=np.uint64))
+        sample[i] = a[np.minimum((u * a.size).astype(np.int64), a.size - 1)]
+        del a
+        f.close()
+    for name, arr in (("jpx_len", lens), ("jpx_bytesum", sums), ("jpx_sample", sample)):
+        np.save(os.path.join(dirname, f"{prefix}{name}.npy"), arr)
+
+
 def run(args):
     import threading
 
@@ -385,8 +421,9 @@ def run(args):
     tif = im.tiff_bytes(img, rows_per_strip=64)
     lay, offs = jp2hip.tiff_layout(tif)
     d_src = torch.frombuffer(bytearray(tif), dtype=torch.uint8).to(device)
+    pcie = args.full and not args.no_pcie
     # the same TIFF in pinned host memory, for the PCIe-inclusive variant
-    h_src = torch.frombuffer(bytearray(tif), dtype=torch.uint8).pin_memory()
+    h_src = torch.frombuffer(bytearray(tif), dtype=torch.uint8).pin_memory() if pcie else None
     torch.cuda.synchronize()
     # `inflight` independent images per GPU, each on its own libjp2hip
     # context (own HIP stream and buffers): the batch path's per-GPU queue.
@@ -410,7 +447,7 @@ def run(args):
             all_stats.append(st.as_dict())
     # single-image latency (one context, nothing else in flight)
     lat, alone = [], []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         t = time.perf_counter()
         _, st = encs[0].encode_device(d_src.data_ptr(), d_src.numel(), lay, jp2hip.LOSSY, rc)
         lat.append(time.perf_counter() - t)
@@ -419,8 +456,11 @@ def run(args):
 
     host_delay = float(os.environ.get("JP2HIP_BENCH_HOST_DELAY_MS", "0")) / 1e3
 
-    def timed(encode):
-        """K steps over the contexts from a shared counter; (seconds, stats)."""
+    def timed(encode, keep=None):
+        """K steps over the contexts from a shared counter; (seconds, stats).
+        `keep` (a list) receives (image index, Output) of the last step's
+        images, left open in the library's pinned buffers (no copy inside the
+        timed region); the caller closes them."""
         stages, errors = [], []
         nxt = [0]
         mu = threading.Lock()
@@ -442,7 +482,10 @@ def run(args):
                     # the Python work between two encodes holds the GIL the
                     # other 15 workers need
                     ok = out.tail(2) == b"\xff\xd9"
-                    out.close()
+                    if keep is not None and step >= total - batch:
+                        keep.append((step, out))
+                    else:
+                        out.close()
                     if not ok:
                         raise RuntimeError("encode output does not end in EOC")
                     stages.append(st)  # (list.append is atomic under the GIL)
@@ -464,15 +507,30 @@ def run(args):
             raise errors[0]
         return dt, [s.as_dict() for s in stages]
 
+    kept = None
+    if args.dump_outputs:
+        # the last step's files stay in their pinned buffers until the timed
+        # region is over: a step's files and one more per context held at once
+        # here, untimed, so the library's pool has the buffers and the timed
+        # region pins none
+        kept = [e.encode_device(d_src.data_ptr(), d_src.numel(), lay, jp2hip.LOSSY, rc, copy=False)[0]
+                for e in encs for _ in range(-(-batch // nf) + 1)]
+        for out in kept:
+            out.close()
+        kept = []
     # the contract's value: TIFF resident in HBM -> JPX bytes in host memory
-    dt, stages = timed(lambda e: e.encode_device(d_src.data_ptr(), d_src.numel(), lay, jp2hip.LOSSY, rc, copy=False))
+    dt, stages = timed(lambda e: e.encode_device(d_src.data_ptr(), d_src.numel(), lay, jp2hip.LOSSY, rc, copy=False),
+                       keep=kept)
     dt_max = barrier_max(world, dt, device)
+    if kept is not None:
+        dump_outputs(args.dump_outputs, [out for _, out in sorted(kept, key=lambda x: x[0])],
+                     prefix=f"rank{rank}_" if world > 1 else "")
     mp = img.shape[0] * img.shape[1] / 1e6
     value = world * mp * total / dt_max
     # PCIe-inclusive: TIFF bytes in pinned host memory -> jp2hip_encode_tiff
     # (header parse, H2D of the 72 MB file, encode) -> JPX bytes in host memory
     dt_h_max = None
-    if not args.no_pcie:
+    if pcie:
         dt_h, _ = timed(lambda e: e.encode_tiff_ptr(h_src.data_ptr(), h_src.numel(), jp2hip.LOSSY, rc, copy=False))
         dt_h_max = barrier_max(world, dt_h, device)
     res = None
@@ -497,7 +555,8 @@ def run(args):
         ach = mq_alg / (avg_all["t1_mq_ms"] * 1e-3) / 1e9 if avg_all["t1_mq_ms"] > 0 else 0.0
         ce = coef_bytes(8, True)
         dwt_alg = dwt_bytes_per_px(C, 1, L, ce) * npx
-        dwt_alone = float(np.mean([x["dwt_ms"] for x in alone]))
+        # (the single-image figures below need the --full run's encodes alone)
+        dwt_alone = float(np.mean([x["dwt_ms"] for x in alone])) if alone else 0.0
         traffic, traffic_src = pmc_traffic(dom)
         # SURVEY.md 8(d) full path: B_path = B_dwt + (coefficient read) C +
         # 3*bpp/8 per pixel (4C there: 4-byte coefficients)
@@ -519,9 +578,9 @@ def run(args):
                        "parallelism": f"replicas x{world}", "ranks_in_process_group": ranks_seen(world),
                        "out_bytes": int(avg["out_bytes"]),
                        "bpp": round(8 * avg["out_bytes"] / npx, 4),
-                       "single_image_latency_ms": round(1e3 * min(lat), 3),
-                       "host_waits_per_encode": int(max(a["host_waits"] for a in alone)),
-                       "rate_iterations": int(max(a["rate_iterations"] for a in alone))},
+                       "single_image_latency_ms": round(1e3 * min(lat), 3) if lat else None,
+                       "host_waits_per_encode": int(max(a["host_waits"] for a in alone)) if alone else None,
+                       "rate_iterations": int(max(a["rate_iterations"] for a in (alone or every)))},
             # the same steps with the TIFF in pinned host memory and the H2D
             # inside the timed span (PCIe-inclusive rate)
             "value_pcie_inclusive": ({"value": round(world * mp * total / dt_h_max, 3), "unit": "MP/s",
@@ -552,10 +611,11 @@ def run(args):
                              "alg_bytes_per_px": round(dwt_bytes_per_px(C, 1, L, ce), 3),
                              "coef_bytes": ce,
                              "stage_ms": round(avg["dwt_ms"], 4),
-                             "alone": {"stage_ms": round(dwt_alone, 4),
-                                       "achieved": round(dwt_alg / (dwt_alone * 1e-3) / 1e9, 2),
-                                       "frac": round(dwt_alg / (dwt_alone * 1e-3) / HBM_PEAK, 5)}}
-                             if avg["dwt_ms"] > 0 and dwt_alone > 0 else None),
+                             "alone": ({"stage_ms": round(dwt_alone, 4),
+                                        "achieved": round(dwt_alg / (dwt_alone * 1e-3) / 1e9, 2),
+                                        "frac": round(dwt_alg / (dwt_alone * 1e-3) / HBM_PEAK, 5)}
+                                       if dwt_alone > 0 else None)}
+                             if avg["dwt_ms"] > 0 else None),
             # SQ counters are per launch (one launch per image: sq_summary.py
             # averages the rocprofv3 --pmc rows over the launches)
             "t1_counters": {"units": "per kernel launch (one per image)",
@@ -567,7 +627,7 @@ def run(args):
             "t1": {"codeblocks": int(avg["codeblocks"]), "coded_passes": int(avg["coded_passes"]),
                    "mq_bytes": int(avg["t1_bytes"]), "mq_decisions": int(avg["mq_decisions"])},
         }
-    if rank == 0:
+    if rank == 0 and args.full:
         res["validation"] = validate_c2(encs[0], d_src, lay, rc, img, rank)
     for e in encs[1:]:  # their HBM and streams back before the lossless legs
         e.close()
@@ -829,18 +889,29 @@ def main():
                     help="independent images in flight per GPU (separate contexts/streams)")
     ap.add_argument("--batch", type=int, default=0,
                     help="images per step (default: --inflight); value = MP of every image / time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lossless", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive C2 leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's JPX files to DIR as .npy arrays "
+                         "(their lengths, byte sums and a fixed seeded sample of their bytes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed C2 steps also run every other leg and check: single-image latency, "
+                         "PCIe-inclusive leg, validation, lossless C3/C4, file spans, C5, CPU baselines "
+                         "(minutes; the --no-* options below trim it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-lossless", action="store_true", help="with --full: skip the lossless C3/C4 legs")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the PCIe-inclusive C2 leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="C2 timed leg only: no PCIe-inclusive leg, lossless C3/C4, file-span, C5 or CPU "
-                         "baselines (the profiled configuration)")
+                    help="with --full: C2 only (latency, timed steps, validation): no PCIe-inclusive leg, "
+                         "lossless C3/C4, file-span, C5 or CPU baselines (the profiled configuration)")
     ap.add_argument("--workload", choices=("c2", "c4", "c5"), default="c2",
                     help="c2: the headline (replicas); c4: CSV batch through the native per-GPU queue; "
                          "c5: one oversized image tile-split across ranks")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs is implemented for --workload c2")
+    if not args.full:
+        args.no_extras = True
     if args.no_extras:
         args.no_pcie = args.no_lossless = args.no_cpu_baseline = True
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:

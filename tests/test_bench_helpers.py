@@ -36,5 +36,46 @@ def test_cli_parses():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode == 0, r.stderr
-    for flag in ("--gpus", "--steps", "--warmup", "--workload"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--full", "--dump-outputs"):
         assert flag in r.stdout
+
+
+class _File:
+    """What bench.dump_outputs takes: an encode's Output, here over bytes."""
+
+    def __init__(self, data):
+        self.data, self.closed = data, False
+
+    def view(self):
+        return memoryview(self.data)
+
+    def close(self):
+        self.closed = True
+
+
+def test_dump_outputs_is_a_fixed_sample(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(7)
+    files = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (70001, 1, 65536)]
+    for d in ("a", "b"):
+        fs = [_File(f) for f in files]
+        bench.dump_outputs(str(tmp_path / d), fs)
+        assert all(f.closed for f in fs)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("jpx_len", "jpx_bytesum", "jpx_sample")}
+    for n, arr in a.items():  # the same files give the same arrays, run after run
+        assert np.array_equal(arr, np.load(tmp_path / "b" / f"{n}.npy"))
+    assert a["jpx_len"].dtype == np.float64 and a["jpx_sample"].dtype == np.float32
+    assert a["jpx_len"].tolist() == [70001, 1, 65536]
+    assert a["jpx_bytesum"].tolist() == [float(sum(f)) for f in files]
+    k = a["jpx_sample"].shape[1]
+    assert a["jpx_sample"].shape == (3, k) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    u = np.sort(np.random.default_rng(bench.DUMP_SEED).random(k))
+    for i, f in enumerate(files):
+        want = np.frombuffer(f, np.uint8)[(u * len(f)).astype(np.int64)]
+        assert np.array_equal(a["jpx_sample"][i], want.astype(np.float32))
+    # a changed byte shows: in the sum always, in the sample where it is drawn
+    g = bytearray(files[0])
+    g[(u[0] * len(g)).astype(np.int64)] ^= 1
+    bench.dump_outputs(str(tmp_path / "c"), [_File(bytes(g))])
+    assert np.load(tmp_path / "c" / "jpx_bytesum.npy")[0] != a["jpx_bytesum"][0]
+    assert np.load(tmp_path / "c" / "jpx_sample.npy")[0, 0] != a["jpx_sample"][0, 0]

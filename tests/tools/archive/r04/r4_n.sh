@@ -11,6 +11,6 @@ L=jp2-bucketeer_amd/jp2hip
 [ -n "$NO_SUITE" ] || tail -1 $o/t.log
 AB_ROUNDS=2 bash tests/tools/ab_kt.sh ${1:-r4n}/ab $L/libjp2hip_base.so $L/libjp2hip.so || exit 1
 for t in libjp2hip_base libjp2hip; do
-  JP2HIP_LIBRARY=$L/$t.so timeout -k 10 300 python bench.py --steps 4 --warmup 1 --no-pcie --no-cpu-baseline > $o/full_$t.json 2> $o/full_$t.err || exit 1
+  JP2HIP_LIBRARY=$L/$t.so timeout -k 10 300 python bench.py --full --steps 4 --warmup 1 --no-pcie --no-cpu-baseline > $o/full_$t.json 2> $o/full_$t.err || exit 1
   python -c "import json; d=json.loads(open('$o/full_$t.json').read().strip().splitlines()[-1]); c3=d.get('lossless_c3',{}); print('$t c2', d['value'], 'c3 inflight', c3.get('mp_per_s_inflight_c_api'), 'c3 d2h_ms', c3.get('stages_ms',{}).get('d2h_ms'), 'pcie', c3.get('roofline_pcie'))" | tee -a $o/ab/summary.txt
 done

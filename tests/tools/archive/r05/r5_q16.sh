@@ -14,7 +14,7 @@ for P in $L $B; do
 done
 bash tests/tools/ab_lib.sh ${1:-r5q16}/ab $L $B 2 || exit 1
 export GPU_MAX_HW_QUEUES=16 JP2HIP_KEEP_HW_QUEUES=1
-C="python bench.py --inflight 1 --steps 3 --warmup 1 --no-cpu-baseline --no-lossless"
+C="python bench.py --full --inflight 1 --steps 3 --warmup 1 --no-cpu-baseline --no-lossless"
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "k_" -d $o/p3 -o run --output-format csv -- $C > $o/p3.log 2>&1 || exit 1
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_" -d $o/p4 -o run --output-format csv -- $C > $o/p4.log 2>&1 || exit 1
 python tests/tools/pmc_summary.py --fetch $o/p3 --write $o/p4 --out $o/pmc_traffic.json > $o/traffic.txt || exit 1

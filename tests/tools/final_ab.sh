@@ -12,7 +12,7 @@ mkdir -p $o
 if [ -f jp2-bucketeer_amd/jp2hip/libjp2hip_base.so ]; then
   for i in 1 2; do
     for L in libjp2hip_base libjp2hip; do
-      JP2HIP_LIBRARY=jp2-bucketeer_amd/jp2hip/$L.so timeout -k 10 240 python bench.py --steps 16 --warmup 2 --no-cpu-baseline --no-lossless > $o/b_${L}_$i.json 2> $o/b_${L}_$i.err || exit 1
+      JP2HIP_LIBRARY=jp2-bucketeer_amd/jp2hip/$L.so timeout -k 10 240 python bench.py --full --steps 16 --warmup 2 --no-cpu-baseline --no-lossless > $o/b_${L}_$i.json 2> $o/b_${L}_$i.err || exit 1
       python -c "import json; d=json.loads(open('$o/b_${L}_$i.json').read().strip().splitlines()[-1]); print('$L', $i, d['value'])" | tee -a $o/summary.txt
     done
   done

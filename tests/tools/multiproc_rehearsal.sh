@@ -12,5 +12,5 @@ for conv in lossy lossless; do
   timeout -k 10 300 python tests/tools/split_compare.py $o/parts_$conv $conv > $o/split_$conv.json 2>> $o/split_$conv.log || exit 1
   rm -rf $o/parts_$conv
 done
-timeout -k 10 300 $R --master-port 29614 bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline --no-lossless > $o/bench_c2_n2.json 2> $o/bench_c2_n2.err || exit 1
+timeout -k 10 300 $R --master-port 29614 bench.py --full --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline --no-lossless > $o/bench_c2_n2.json 2> $o/bench_c2_n2.err || exit 1
 timeout -k 10 400 $R --master-port 29615 bench.py --gpus 2 --workload c5 --steps 2 --warmup 1 > $o/bench_c5_n2.json 2> $o/bench_c5_n2.err || exit 1

@@ -7,6 +7,6 @@ o=gpurun_out/${1:-sdma_probe}
 mkdir -p $o
 for v in unset 0 1; do
   if [ $v = unset ]; then unset HSA_ENABLE_SDMA; else export HSA_ENABLE_SDMA=$v; fi
-  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $o/kt_$v -o run --output-format csv -- python bench.py --steps 2 --warmup 1 --no-extras > $o/b_$v.json 2> $o/b_$v.err || exit 1
+  timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $o/kt_$v -o run --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-extras > $o/b_$v.json 2> $o/b_$v.err || exit 1
   echo "SDMA=$v: $(grep -c copyBuffer $o/kt_$v/run_kernel_trace.csv) copyBuffer dispatches, value $(python -c "import json;print(json.loads(open('$o/b_$v.json').read().strip().splitlines()[-1])['value'])")" | tee -a $o/summary.txt
 done
