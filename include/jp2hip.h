@@ -55,20 +55,23 @@ typedef struct jp2hip_config {
 typedef struct jp2hip_recipe {
     int32_t levels;          /* Clevels=6                                      */
     int32_t layers;          /* Clayers=6                                      */
-    int32_t tile_w, tile_h;  /* Stiles={512,512}                               */
+    int32_t tile_w, tile_h;  /* Stiles={512,512}; at most 65535 tiles          */
     int32_t cblk_w_log2;     /* Cblk={64,64}                                   */
     int32_t cblk_h_log2;
     int32_t nprecincts;      /* Cprecincts={256,256},{256,256},{128,128}:     */
-    int32_t prec_w_log2[16]; /*   highest resolution first, last one repeats   */
+    int32_t prec_w_log2[16]; /*   highest resolution first, last one repeats;  */
+                             /*   0..16 entries (0: one precinct), each 0..15, */
+                             /*   0 only for the lowest resolution             */
     int32_t prec_h_log2[16];
     int32_t progression;     /* Corder=RPCL (2); the only order implemented    */
     int32_t sop, eph;        /* Cuse_sop=yes Cuse_eph=yes                      */
     int32_t plt;             /* ORGgen_plt=yes                                 */
     int32_t tparts_r;        /* ORGtparts=R                                    */
-    int32_t guard_bits;      /* 1                                              */
+    int32_t guard_bits;      /* 1 (0..7: three bits of Sqcd)                   */
     int32_t reversible;      /* Creversible=yes -> 5/3 + RCT, else 9/7 + ICT   */
     int32_t mct;             /* colour transform on components 0..2            */
-    double qstep;            /* irreversible base step (Kakadu Qstep=1/256)    */
+    double qstep;            /* irreversible base step (Kakadu Qstep=1/256):   */
+                             /* finite, > 0, no band over 30 bit-planes        */
     double rate_bpp;         /* "-rate 3"; <= 0 means "-rate -" (all passes)   */
     int32_t format;          /* JP2HIP_FORMAT_*                                */
     int32_t comment;         /* emit Kakadu-style COM markers: a version       */

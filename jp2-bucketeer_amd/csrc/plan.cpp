@@ -201,6 +201,31 @@ bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits
         err = "code-block size must be 4..64";
         return false;
     }
+    // fields the main header packs into fewer bits than an int32: a value out
+    // of range would wrap there and give a file that says something else
+    if (rc.guard_bits < 0 || rc.guard_bits > 7) {  // Sqcd: 3 bits
+        err = "guard_bits must be 0..7";
+        return false;
+    }
+    if (!rc.reversible && !(std::isfinite(rc.qstep) && rc.qstep > 0.0)) {
+        err = "qstep must be finite and above 0";
+        return false;
+    }
+    if (rc.nprecincts < 0 || rc.nprecincts > 16) {
+        err = "nprecincts must be 0..16";
+        return false;
+    }
+    for (int r = 0; r <= rc.levels; r++) {  // SPcod: 4 bits each; 0 only where no band is halved (B.6)
+        const int px = prec_log2(rc, r, false), py = prec_log2(rc, r, true), lo = r ? 1 : 0;
+        if (px < lo || px > 15 || py < lo || py > 15) {
+            err = "prec_w_log2 / prec_h_log2 must be 0..15 (1..15 above resolution 0)";
+            return false;
+        }
+    }
+    if (cdiv(w, rc.tile_w) * cdiv(h, rc.tile_h) > 65535) {  // Isot: 16 bits
+        err = "more than 65535 tiles (tile_w x tile_h is too small for the image)";
+        return false;
+    }
     P = Plan();
     P.rc = rc;
     P.w = w; P.h = h; P.nc = nc; P.bits = bits;

@@ -1694,6 +1694,23 @@ int oracle_encode(const void *pix, int w, int h, int nc, int bits, const oracle_
     if ((rc->tile_w % (1 << rc->levels)) || (rc->tile_h % (1 << rc->levels))) {
         set_err("encode: tile size must be a multiple of 2^levels"); return -1;
     }
+    /* fields the main header packs into fewer bits than an int (Sqcd 3, SPcod
+     * 4 + 4, Isot 16): out of range they would wrap there */
+    if (rc->guard_bits < 0 || rc->guard_bits > 7) { set_err("encode: guard_bits must be 0..7"); return -1; }
+    if (!rc->reversible && !(isfinite(rc->qstep) && rc->qstep > 0.0)) {
+        set_err("encode: qstep must be finite and above 0"); return -1;
+    }
+    if (rc->nprecincts < 0 || rc->nprecincts > 16) { set_err("encode: nprecincts must be 0..16"); return -1; }
+    for (int r = 0; r <= rc->levels; r++) {
+        int px = prec_log2(rc, r, 0), py = prec_log2(rc, r, 1), lo = r ? 1 : 0;
+        if (px < lo || px > 15 || py < lo || py > 15) {
+            set_err("encode: prec_w_log2 / prec_h_log2 must be 0..15 (1..15 above resolution 0)"); return -1;
+        }
+    }
+    if (rc->tile_w <= 0 || rc->tile_h <= 0 ||
+        ceil_div64(w, rc->tile_w) * ceil_div64(h, rc->tile_h) > 65535) {
+        set_err("encode: more than 65535 tiles (tile_w x tile_h is too small for the image)"); return -1;
+    }
     encoder E;
     memset(&E, 0, sizeof E);
     E.rc = rc; E.w = w; E.h = h; E.nc = nc; E.bits = bits;

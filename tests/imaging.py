@@ -339,6 +339,112 @@ def tile_parts(cs: bytes):
     return out
 
 
+def expected_packets(cs: bytes) -> int:
+    """Packet count of a code-stream from its geometry alone (SIZ and COD,
+    B.5-B.6; tiles anchored at 0, no subsampling): sum over tiles and
+    resolutions of npx * npy * components * layers."""
+    seg = main_header_segments(cs)
+    siz, cod = seg["ff51"], seg["ff52"]
+    w, h = struct.unpack(">II", siz[6:14])
+    tw, th = struct.unpack(">II", siz[22:30])
+    nc = struct.unpack(">H", siz[38:40])[0]
+    layers = struct.unpack(">H", cod[6:8])[0]
+    L = cod[9]
+    if cod[4] & 1:
+        pp = [(cod[14 + r] & 15, cod[14 + r] >> 4) for r in range(L + 1)]
+    else:
+        pp = [(15, 15)] * (L + 1)
+
+    def count(a0, a1, sh, p):  # precincts of [a0, a1) at a resolution 2^sh below full
+        r0, r1 = a0 >> sh, -((-a1) >> sh)
+        return (-((-r1) >> p)) - (r0 >> p) if r1 > r0 else 0
+
+    n = 0
+    for y0 in range(0, h, th):
+        for x0 in range(0, w, tw):
+            for r in range(L + 1):
+                n += (count(x0, min(w, x0 + tw), L - r, pp[r][0]) *
+                      count(y0, min(h, y0 + th), L - r, pp[r][1]) * nc * layers)
+    return n
+
+
+def tile_part_walk(cs: bytes, sop: int):
+    """Independent reader of every tile-part of a code-stream (A.4.2, A.7.3,
+    A.8.1): SOT, then the marker segments by their lengths up to SOD (no
+    search for marker bytes), PLT 7-bit groups decoded across segments.
+    Returns per tile-part (Isot, TPsot, TNsot, n_plt_segments,
+    packet_lengths) and asserts what a reader relies on: Zplt counts 0, 1, 2,
+    ... within a tile-part, no segment is longer than 65535 bytes (its Lplt
+    agrees with where the next marker is), no length straddles two segments,
+    the lengths sum to Psot less the tile-part header, EOC follows the last
+    tile-part, with sop=1 every packet starts with FF91 0004 Nsop (Nsop
+    counting up per tile, modulo 65536), and the packet count is the one the
+    geometry gives.  Scod's SOP bit must agree with `sop`.  Without PLT the
+    packets cannot be located, so the packet checks are left out (n_plt_segments
+    is 0 then: a caller that knows the recipe checks that)."""
+    cs = codestream(cs)
+    assert cs[:2] == b"\xff\x4f"
+    p = 2
+    while cs[p:p + 2] != b"\xff\x90":  # main header: segment by segment
+        assert cs[p] == 0xFF, f"no marker at byte {p}"
+        p += 2 + struct.unpack(">H", cs[p + 2:p + 4])[0]
+    scod = main_header_segments(cs)["ff52"][4]
+    assert bool(scod & 2) == bool(sop), f"Scod {scod:#x} vs sop={sop}"
+    out = []
+    nsop = {}  # per tile: packets so far
+    seen_tp = {}
+    npk = 0
+    any_plt = False
+    while cs[p:p + 2] == b"\xff\x90":
+        lsot, isot, psot, tp, tn = struct.unpack(">HHIBB", cs[p + 2:p + 12])
+        assert lsot == 10 and psot >= 14 and p + psot <= len(cs), f"SOT at {p}: Lsot {lsot} Psot {psot}"
+        assert tp == seen_tp.get(isot, 0), f"tile {isot}: TPsot {tp} after {seen_tp.get(isot, 0)} tile-parts"
+        seen_tp[isot] = tp + 1
+        assert tn == 0 or tp < tn, f"tile {isot}: TPsot {tp} with TNsot {tn}"
+        q = p + 12
+        lens, nseg, cur, open_len = [], 0, 0, False
+        while cs[q:q + 2] != b"\xff\x93":
+            assert cs[q] == 0xFF and q < p + psot, f"tile-part at {p}: no marker at byte {q}"
+            n = struct.unpack(">H", cs[q + 2:q + 4])[0]  # <= 65535 by construction: what matters
+            assert n >= 2 and q + 2 + n <= p + psot - 2   # is that the next marker follows it
+            if cs[q + 1] == 0x58:
+                assert n >= 3 and cs[q + 4] == nseg, f"tile-part at {p}: Zplt {cs[q + 4]} in segment {nseg}"
+                assert not open_len, f"tile-part at {p}: a length straddles PLT segments {nseg - 1} and {nseg}"
+                for b in cs[q + 5:q + 2 + n]:
+                    cur = (cur << 7) | (b & 0x7F)
+                    open_len = bool(b & 0x80)
+                    if not open_len:
+                        lens.append(cur)
+                        cur = 0
+                assert not open_len, f"tile-part at {p}: PLT segment {nseg} ends inside a length"
+                nseg += 1
+            q += 2 + n
+        body = q + 2
+        if nseg:
+            any_plt = True
+            assert sum(lens) == p + psot - body, f"tile-part at {p}: PLT sums to {sum(lens)}, body is {p + psot - body}"
+            if sop:
+                o = body
+                k = nsop.get(isot, 0)
+                for n in lens:
+                    assert n >= 6 and cs[o:o + 4] == b"\xff\x91\x00\x04", f"no SOP at byte {o}"
+                    assert struct.unpack(">H", cs[o + 4:o + 6])[0] == k & 0xFFFF, f"Nsop at byte {o}"
+                    k += 1
+                    o += n
+            nsop[isot] = nsop.get(isot, 0) + len(lens)
+            npk += len(lens)
+        out.append((isot, tp, tn, nseg, lens))
+        p += psot
+    assert cs[p:] == b"\xff\xd9", f"no EOC after the last tile-part (byte {p} of {len(cs)})"
+    last_tn = {x[0]: x[2] for x in out}
+    for t, n in seen_tp.items():
+        assert last_tn[t] == n, f"tile {t}: {n} tile-parts, last TNsot {last_tn[t]}"
+    if any_plt:
+        assert all(x[3] > 0 for x in out), "a tile-part without PLT among tile-parts with one"
+        assert npk == expected_packets(cs), f"{npk} packets in the PLTs, geometry gives {expected_packets(cs)}"
+    return out
+
+
 def tiff_set_tag(data: bytes, tag: int, value: int) -> bytes:
     """Classic or BigTIFF (either byte order): overwrite the first (inline)
     value of IFD entry `tag` -- malformed-file fixtures for the parser tests."""
