@@ -291,7 +291,7 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
         return fail("tiff: bad TileWidth/TileLength");
     if (tiled && !e_cnt) return fail("tiff: tiles need TileByteCounts");
     // strips: uncompressed, LZW, Deflate or PackBits (decoded on the GPU,
-    // kernels.hip k_unlzw / k_inflate / k_unpackbits); JPEG / CCITT are not
+    // lzw.hip, unpack.hip k_inflate / k_unpackbits); JPEG / CCITT are not
     if (comp != 1 && comp != 5 && comp != 8 && comp != 32946 && comp != 32773)
         return fail("tiff: compression " + std::to_string(comp) +
                     " is not supported (uncompressed, LZW, Deflate and PackBits only)");

@@ -5,6 +5,7 @@
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
+#include <array>
 #include <chrono>
 #include <cstdint>
 #include <functional>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "jp2hip_internal.h"
+#include "stages.h"
 
 namespace jp2hip {
 
@@ -26,117 +28,25 @@ struct StageTimes {
     double ingest = 0, dwt = 0, quant = 0, t1_cm = 0, t1_mq = 0, pcrd = 0, d2h = 0, t2 = 0;
 };
 
-struct T2Args;  // t2_device.hip
+struct T2Args;    // t2_device.hip
+struct FrontJob;  // front.hip
 
-// compressed strips / tiles -> uncompressed staging copy (kernels.hip, lzw.hip)
-struct UnpackArgs {
-    const uint8_t *src;
-    const uint64_t *off, *cnt;  // per strip (tile): byte offset and compressed size
-    int nstrips, per_plane, rps, h;
-    uint64_t row_bytes, stride;  // decoded row and strip stride (bytes)
-    uint64_t unit_bytes;         // tiles: every unit decodes to this many bytes
-    uint8_t *dst;
-    const int *only;  // k_unlzw: decode only strips with only[s] != 0 (nullptr: all)
-    int *err;
-    uint32_t *lnk;    // k_inflate: a link per output byte, strip s at lnk + s * stride
-};
-__host__ __device__ inline uint64_t strip_out_bytes(const UnpackArgs &a, int s) {
-    if (a.unit_bytes) return a.unit_bytes;
-    const int y0 = (s % a.per_plane) * a.rps;
-    return (uint64_t)(a.rps < a.h - y0 ? a.rps : a.h - y0) * a.row_bytes;
-}
-// LZW strips, segment-parallel (lzw.hip): lzw_slices() lays out each
-// strip's segment slots (returns their total), the caller uploads `slice` to
-// the start of `scratch` (lzw_scratch_bytes); false on a launch error
-uint64_t lzw_slices(const uint64_t *strip_bytes, int nstrips, std::vector<uint64_t> &slice);
-size_t lzw_scratch_bytes(int nstrips, uint64_t segs);
-bool launch_lzw(const UnpackArgs &u, uint64_t segs, void *scratch, hipStream_t st);
-
-// the SDMA engines chosen per GPU and their probed rates (t2_device.hip)
-std::string dma_engine_report();
-
-// tier-1 kernels (t1.hip)
-#ifndef JP2HIP_ORDER_SUB
-#define JP2HIP_ORDER_SUB 16  // MQ lane-order buckets per octave of decision count
-#endif
-constexpr int kOrderSub = JP2HIP_ORDER_SUB;
-constexpr int kOrderBuckets = 32 * kOrderSub;  // MQ lane-order buckets (decision count, 6.25 % wide)
-// Work lists of k_t1_cm3, filled once the coded planes are known
-// (emit_t1_items: k_plane_pmin, or k_t1_items without slope prediction):
-// list k holds the blocks with more than k coded planes (item = plane k from
-// the top of that block), in no particular order.
-struct T1ItemArgs {
-    int nb, kmax;               // kmax: largest Mb of the plan (<= 64)
-    const uint8_t *P;
-    uint8_t *pmin;              // k_t1_items writes 0 (every plane coded)
-    uint32_t *dfill;            // [64] list fills (zeroed by k_quant)
-    int32_t *dlist;             // [kmax][nb]
-    unsigned long long *acc;    // [nb] (coded planes << 40): k_t1_cm3 counts planes down, decisions up
-    uint8_t *npasses;           // blocks without a coded plane: 0 passes, 0 bytes (k_t1_mq never sees them)
-    int32_t *lengths;
-    // decision-stream slots, placed here (emit_t1_items)
-    const BlockDesc *blocks;
-    unsigned long long *pool_used;  // zeroed by k_quant; ends at the bytes needed
-    unsigned long long pool_cap;    // bytes in the pool (stream_buf)
-    uint64_t *slot_off;             // [nb]
-    int *err;                       // kErrSlotPool when a block did not fit
-};
-struct T1CmArgs {
-    const uint32_t *dfill;  // per-depth list fills
-    const int32_t *dlist;
-    int nb, kmax;
-    int max_items;          // bound on the items (nb * kmax): the grid
-    const BlockDesc *blocks;
-    const uint64_t *bp;
-    const int32_t *sm;
-    const uint8_t *P;
-    uint8_t *stream;
-    const uint64_t *slot_off;
-    uint4 *counts;    // [block][32] (end of SPP, end of MRP, end of CUP)
-    int64_t *dspp;    // [block][32]
-    unsigned long long *acc;  // [block] (planes left << 40) | decisions so far
-    uint32_t *bfill;          // [256] MQ lane-order bucket fills (zeroed by k_quant)
-    int32_t *bslots;          // [256][nb] blocks per bucket
-    int lossless;
-};
-struct T1MqArgs {
-    const BlockDesc *blocks;
-    const uint32_t *bfill;   // lane order: bucket fills and members (k_t1_cm3)
-    const int32_t *bslots;
-    int nblocks;
-    const uint8_t *P;
-    const uint8_t *pmin;  // lowest coded plane (slope prediction; 0 = all)
-    const uint8_t *stream;
-    const uint64_t *slot_off;
-    const uint4 *counts;
-    const int64_t *dspp, *dref, *dsig;
-    uint8_t *out;
-    int32_t *rates;
-    int64_t *dists;
-    uint8_t *npasses;
-    int32_t *lengths;
-    int *err;
-    unsigned long long *span;  // [2] execution span in 100 MHz ticks (~min start, max end)
-    int64_t *dbg;  // optional per-block census [block][6] (debug builds: decisions, modeller cycles
-                   // and barrier cycles, coder cycles and barrier cycles, lane position)
-};
-// fused ingest + DWT (dwt.hip)
-struct DwtLaunch {
-    const void *tif;
-    const uint64_t *strip_off;
-    int rps, img_w, nc, bits, planar, big_endian, mct, spp_strips;
-    int ntx, tile_w, tile_h, row0, plane_w, plane_h, ntc, levels, reversible;
-    int last_tile_w;  // width of the last tile column (the others are tile_w)
-    const int32_t *tc_w, *tc_h;
-    void *coef, *scratch0, *scratch1;  // scratch: ntc * ceil(plane_w/2) * ceil(plane_h/2) words each
-    QuantTab qt;                       // final coefficients are written as quantisation indices
-};
-bool launch_dwt(const DwtLaunch &p, hipStream_t st);
-
-void launch_t1_cm(const T1CmArgs &a, hipStream_t st);
-void launch_t1_items(const T1ItemArgs &a, hipStream_t st);
-void launch_t1_mq(const T1MqArgs &a, hipStream_t st);
-uint32_t t1_plane_stream_cap(int w, int h);
+// Every device buffer of a context, named once: the DevBuf members and
+// bufs() (need accounting, trim, the destructor) both come from this list.
+#define JP2HIP_DEVBUFS(X)                                                                                     \
+    X(coef) X(blocks) X(order) X(bp) X(sm) X(P) X(dref) X(dsig) X(t1out) X(rates) X(dists) X(npasses)         \
+    X(lengths) X(weight) X(nhull) X(hpass) X(hkey) X(budget) X(nl) X(lrate) X(err) X(tcw) X(tch) X(strips)    \
+    X(src) X(segcnt) X(segoff) X(est) X(hist) X(pmin) X(mqspan) X(stage) X(soff) X(lzwseg) X(untiled)         \
+    X(inflnk) X(segkey) X(llbuf0) X(llbuf1) X(ordkey) X(segval) X(thr) X(items) X(slotoff) X(stream_buf)      \
+    X(counts) X(dspp) X(dbgbuf) X(t1fill) X(dbgsel)                                                           \
+    /* PCRD selection (k_hull / k_select): slope-bin histogram, ticket + list fills, candidate lists */      \
+    X(pcrd_hb) X(pcrd_hc) X(sel_ctl) X(sel_key) X(sel_size)                                                   \
+    /* rate-control groups (Plan::grp_b0, then each group's first candidate slot) and each group's */        \
+    /* tier-1 bytes (k_hull) */                                                                               \
+    X(grptab) X(gtot)                                                                                         \
+    /* device tier-2 (t2_device.hip) */                                                                       \
+    X(hdist) X(rstate) X(t2ticket) X(t2prec) X(t2tp) X(t2tt) X(t2lblock) X(t2incl) X(t2pklen) X(t2pkoff)      \
+    X(t2tplen) X(t2tphdr) X(t2tpoff) X(t2blkdst) X(t2out) X(t2sum)
 
 // Owns all device memory of a context; buffers only grow while the context
 // stays within its soft limit, so repeated encodes of the same geometry never
@@ -258,6 +168,16 @@ class GpuEncoder {
   private:
     // debug: JP2HIP_DUMP_DIR=<dir> writes every stage's device buffer
     bool dump(const char *dir, const char *name, const DevBuf &b, size_t bytes, std::string &err);
+    // run_front's stages, in its order (front.hip; hull_launch: pcrd.hip)
+    bool front_reserve(FrontJob &j, std::string &err);
+    bool front_upload(const FrontJob &j, std::string &err);
+    bool front_first_args(FrontJob &j, std::string &err);
+    bool front_ingest_dwt(const FrontJob &j, std::string &err);
+    bool front_quant(const FrontJob &j, std::string &err);
+    bool front_predict_items(const FrontJob &j, std::string &err);
+    bool front_t1(const FrontJob &j, std::string &err);
+    bool hull_launch(const Plan &plan, std::string &err);
+    bool front_dumps(const FrontJob &j, std::string &err);
     bool apply_thresholds(const Plan &plan, const int *halt, std::string &err);
     void select_launch(const Plan &plan, const int *halt, const RateState *init = nullptr, RateState *rs = nullptr);
     T2Args t2_args(const Plan &plan) const;
@@ -291,27 +211,34 @@ class GpuEncoder {
     std::vector<PinnedChunk> stg;
     size_t stg_used = 0;
     hipEvent_t stg_ev = nullptr;  // after the last staged copy
-    static constexpr int kNumEvents = 12;
+    // Timing events on the stream, in the order an encode records them; what
+    // lies between two of them is a StageTimes field (collect_profile,
+    // t2_size, rate_loop, t2_emit).
+    enum Ev {
+        kEvFrontBegin,   // run_front: .. kEvDwtBegin = ingest (nothing is launched between them)
+        kEvDwtBegin,     // .. kEvDwtEnd = dwt (k_ingest when there is no decomposition)
+        kEvDwtEnd,       // .. kEvQuantEnd = quant (quantiser, slope prediction, tier-1 items)
+        kEvQuantEnd,
+        kEvCmBegin,      // .. kEvCmEnd = t1_cm
+        kEvCmEnd,        // .. kEvMqEnd = t1_mq
+        kEvMqEnd,        // .. kEvHullEnd = pcrd (k_hull)
+        kEvHullEnd,
+        kEvSelectBegin,  // .. kEvSelectEnd = pcrd (k_select, k_apply); .. kEvT2End = t2 (rate_loop)
+        kEvSelectEnd,
+        kEvT2Begin,      // .. kEvT2End = t2 (t2_size) or d2h (t2_emit)
+        kEvT2End,
+        kNumEvents
+    };
     int device = 0;
     int waits = 0;
     hipEvent_t sync_ev = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev[kNumEvents] = {};
-    DevBuf coef, blocks, order, bp, sm, P, dref, dsig, t1out, rates, dists, npasses, lengths, weight,
-        nhull, hpass, hkey, budget, nl, lrate, dstoff, packed, err, tcw, tch, strips, src, segcnt, segoff,
-        est, hist, kcut, pmin, mqspan, stage, soff, lzwseg, untiled, inflnk, segkey, llbuf0, llbuf1, ordkey, segval, thr, items,
-        slotoff, stream_buf, counts, dspp, dbgbuf, t1fill, dbgsel;
-    // PCRD selection (k_hull / k_select): slope-bin histogram, ticket + list
-    // fills, candidate lists
-    DevBuf pcrd_hb, pcrd_hc, sel_ctl, sel_key, sel_size;
-    // rate-control groups (Plan::grp_b0, then each group's first candidate
-    // slot) and each group's tier-1 bytes (k_hull)
-    DevBuf grptab, gtot;
-    // device tier-2 (t2_device.hip)
-    DevBuf hdist, rstate, t2ticket;
+#define X(name) DevBuf name;
+    JP2HIP_DEVBUFS(X)
+#undef X
     RateState *h_rs = nullptr;      // host-mapped: rate state, then the T2Summary (k_rate_step)
     RateState *d_rs_out = nullptr;  // its device address
-    DevBuf t2prec, t2tp, t2tt, t2lblock, t2incl, t2pklen, t2pkoff, t2tplen, t2tphdr, t2tpoff, t2blkdst, t2out, t2sum;
     int t2_nprec = 0, t2_ntp = 0;
     bool t2_wave = true;  // precincts of <= 64 blocks: k_t2_wave (layer assignment fused in)
     uint64_t front_gen = 0, t2_gen = 0;  // plan generation whose tables are resident
@@ -319,8 +246,6 @@ class GpuEncoder {
     int64_t *h_tot = nullptr;  // pinned [8]: t1 total, -, k_t1_mq span[2], unpack error, segment tail[2]
     bool profiled = false;
     int nseg = 0;  // hull segments at most: the bound sum(3 Mb - 2)
-    uint8_t *h_packed = nullptr;
-    size_t h_packed_cap = 0;
     std::vector<int64_t> h_hist;
     std::vector<uint64_t> strips_host;  // strip offsets last uploaded to `strips`
     const void *strips_dev = nullptr;
@@ -337,7 +262,12 @@ class GpuEncoder {
     uint64_t pool_hint = 0;
     int pool_grows = 0;
     double pool_frac_test = -1.0;  // JP2HIP_TEST_POOL_FRAC (tests: force the grow path)
-    std::vector<DevBuf *> bufs();
+#define X(name) +1
+    static constexpr int kNumBufs = 0 JP2HIP_DEVBUFS(X);
+#undef X
+#define X(name) &name,
+    std::array<DevBuf *, kNumBufs> bufs() { return {{JP2HIP_DEVBUFS(X)}}; }
+#undef X
 };
 
 // Grows b to at least count T's (12.5 % headroom), within the hard limit.

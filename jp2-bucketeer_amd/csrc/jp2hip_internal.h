@@ -1,5 +1,5 @@
 // jp2hip_internal.h -- host-side model of one encode (geometry, quantiser,
-// code-block table) shared by the HIP launch code (kernels.hip), tier-2
+// code-block table) shared by the HIP launch code (the .hip stage files), tier-2
 // (t2.cpp) and the C ABI (api.cpp).
 #pragma once
 
@@ -12,13 +12,13 @@
 namespace jp2hip {
 
 constexpr int kMaxPasses = 96;    // 3*32-2 rounded up; per-block pass table stride
-// slope prediction (kernels.hip k_plane_*, oracle predict_and_code): 1/8-octave
+// slope prediction (front.hip k_plane_*, oracle predict_and_code): 1/8-octave
 // bins of the double slope's bit pattern covering 2^-64 .. 2^64, and the
 // margin (bins) kept below the predicted rate-target bin
 constexpr int kSlopeBins = 1024;
 constexpr int kSlopeBinBase = (1023 - 64) << 3;
 constexpr int kSkipMargin = 12;
-// PCRD threshold selection (kernels.hip k_hull / k_select): hull segment bytes
+// PCRD threshold selection (pcrd.hip k_hull / k_select): hull segment bytes
 // histogrammed over 1/32-octave bins of the slope key (bits 47..62 of the
 // IEEE double, 2^-64 .. 2^64, clamped at both ends); the exact threshold is
 // then resolved inside the one bin where a layer's budget falls
@@ -64,7 +64,7 @@ struct BlockDesc {
     float inv_delta;    // irreversible quantiser reciprocal
     uint32_t pad2;
     uint64_t bp_off;    // bit-plane storage offset, in uint64 words: (Mb+1)*64 column masks
-                        // (kernels.hip k_quant)
+                        // (front.hip k_quant)
     uint64_t sm_off;    // sign-magnitude storage offset, in int32 words
     uint64_t out_off;   // tier-1 output offset, bytes
     uint32_t out_cap;   // tier-1 output capacity, bytes
@@ -186,8 +186,8 @@ struct T2Summary {
     int32_t skipped, err;             // slope prediction skipped planes; tier-1 overflow
     int64_t stream_need;              // decision-stream pool bytes the coded planes took
 };
-// Rate control of a rate-driven encode, run on the device (kernels.hip
-// k_rate_step; the oracle's loop in oracle_encode): iteration `it` selects
+// Rate control of a rate-driven encode, run on the device (pcrd.hip rate_loop,
+// device_common.h rate_step; the oracle's loop in oracle_encode): iteration `it` selects
 // with `budget`, sizes the code-stream, stops when it fits `target` (or after
 // 8 iterations), else lowers the budget.  `halt` stops the remaining
 // iterations' kernels; `safety` = slope prediction's safety net fired

@@ -1,7 +1,7 @@
 // lzw.hip -- TIFF LZW strips (compression 5) decoded segment-parallel.
 //
 // A strip is one MSB-first code stream, and decoding it code by code is a
-// serial chain (k_unlzw in kernels.hip, ~0.35 us per code on one lane).  The
+// serial chain (k_unlzw below, ~0.35 us per code on one lane).  The
 // format has more parallelism than that:
 //
 //  * Between two Clear codes (a *segment*) the dictionary grows by one entry
@@ -36,7 +36,86 @@
 
 namespace jp2hip {
 
-__global__ void k_unlzw(UnpackArgs a);  // kernels.hip (serial fallback)
+// LZW, MSB-first codes of 9..12 bits with TIFF's early width change; the
+// string of table entry k is (start, length) inside the strip's own output
+// (entry k = string(prev) + first byte of the next string, which is exactly
+// where the decoder wrote them), so decoding is copying, as in LZ77.
+// One strip per single-lane workgroup: a strip's decode is one serial chain,
+// so strips must not share a wave (divergent lanes run each other's paths);
+// the 4096-entry string table lives in LDS, and a string is copied 8 bytes
+// of independent loads at a time.
+__global__ void __launch_bounds__(64) k_unlzw(UnpackArgs a) {
+    __shared__ uint2 tab[4096];
+    const int s = blockIdx.x;
+    if (s >= a.nstrips || threadIdx.x || (a.only && !a.only[s])) return;
+    const uint8_t *in = a.src + a.off[s];
+    const uint64_t n = a.cnt[s], cap = strip_out_bytes(a, s);
+    uint8_t *out = a.dst + (uint64_t)s * a.stride;
+    uint64_t ip = 0, pos = 0, acc = 0, prev_pos = 0;
+    int nbits = 0, width = 9, next = 258;
+    uint32_t prev_len = 0;
+    bool bad = false;
+    if (n >= 2 && in[0] == 0 && (in[1] & 1)) {  // pre-TIFF 6.0 (LSB-first) LZW, as libtiff detects it
+        atomicOr(a.err, 4);
+        return;
+    }
+    for (;;) {
+        if (pos >= cap) break;  // strip complete: trailing codes are ignored (libtiff stops here too)
+        if (nbits < width) {  // top up to >= 32 bits with independent byte loads
+            if (ip + 4 <= n) {
+                const uint32_t w4 = ((uint32_t)in[ip] << 24) | ((uint32_t)in[ip + 1] << 16) |
+                                    ((uint32_t)in[ip + 2] << 8) | in[ip + 3];
+                acc = (acc << 32) | w4;
+                ip += 4;
+                nbits += 32;
+            } else {
+                while (nbits < width && ip < n) { acc = (acc << 8) | in[ip++]; nbits += 8; }
+            }
+        }
+        if (nbits < width) break;  // input exhausted: treat as end of information
+        const int code = (int)((acc >> (nbits - width)) & ((1u << width) - 1u));
+        nbits -= width;
+        if (code == 257) break;
+        if (code == 256) { width = 9; next = 258; prev_len = 0; continue; }
+        const uint64_t cur = pos;
+        uint32_t len;
+        if (code < 256) {
+            out[pos++] = (uint8_t)code;
+            len = 1;
+        } else {
+            uint64_t from;
+            bool kwk = false;  // string(prev) + its own first byte: the last byte is the first
+            if (code < next) { const uint2 e = tab[code]; from = e.x; len = e.y; }
+            else if (code == next && prev_len) { from = prev_pos; len = prev_len + 1; kwk = true; }
+            else { bad = true; break; }
+            if (pos + len > cap) {  // the strip ends inside this string: keep what fits
+                for (uint64_t k = 0; pos + k < cap; k++) out[pos + k] = (kwk && k == len - 1) ? out[from] : out[from + k];
+                pos = cap;
+                break;
+            }
+            const uint32_t body = kwk ? len - 1 : len;  // source bytes all lie before pos
+            uint32_t k = 0;
+            for (; k + 8 <= body; k += 8) {
+                uint8_t t[8];
+#pragma unroll
+                for (int j = 0; j < 8; j++) t[j] = out[from + k + j];
+#pragma unroll
+                for (int j = 0; j < 8; j++) out[pos + k + j] = t[j];
+            }
+            for (; k < body; k++) out[pos + k] = out[from + k];
+            if (kwk) out[pos + body] = out[from];
+            pos += len;
+        }
+        if (prev_len && next < 4096) {
+            tab[next] = make_uint2((uint32_t)prev_pos, prev_len + 1);
+            next++;
+            if (next >= (1 << width) - 1 && width < 12) width++;
+        }
+        prev_pos = cur;
+        prev_len = len;
+    }
+    if (bad || pos != cap) atomicOr(a.err, 2);
+}
 
 constexpr int kLzwSegMax = 4096;        // codes of a segment handled in LDS (libtiff: <= 3837)
 constexpr int kLzwScanWin = 16384;      // k_lzw_scan input window (bytes)

@@ -330,7 +330,7 @@ bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits
                                         uint64_t cap = ((uint64_t)bd.w * bd.h * (q.Mb + 1)) / 2 + 1024;
                                         cap = (cap + 15) & ~(uint64_t)15;
                                         bd.out_cap = (uint32_t)cap;
-                                        bpw += (uint64_t)(q.Mb + 1) * 64;  // column masks (kernels.hip k_quant)
+                                        bpw += (uint64_t)(q.Mb + 1) * 64;  // column masks (front.hip k_quant)
                                         smw += (uint64_t)64 * bd.h;
                                         ob += cap;
                                         P.blocks.push_back(bd);

@@ -2,7 +2,7 @@
 // (one oversized image, contiguous bands of tile rows per
 // GPU).  Host-only: no device code, so the exchange is testable on CPU.
 //
-// Single-image rule (kernels.hip k_thresh, oracle/jp2_oracle.c
+// Single-image rule (pcrd.hip k_select, oracle/jp2_oracle.c
 // select_threshold): walk the hull segments of every code-block in
 // decreasing slope-key order and take whole equal-key groups while the
 // running byte total fits the layer budget; the threshold K is the last key

@@ -33,18 +33,11 @@
 
 #include "device_common.h"
 #include "gpu_encoder.h"
+#include "hip_check.h"
 #include "host_wait.h"
+#include "stage_repeat.h"
 
 namespace jp2hip {
-
-#define HIPCHECK(x)                                                                    \
-    do {                                                                               \
-        hipError_t e_ = (x);                                                           \
-        if (e_ != hipSuccess) {                                                        \
-            err = std::string(#x) + ": " + hipGetErrorString(e_);                      \
-            return false;                                                              \
-        }                                                                              \
-    } while (0)
 
 struct T2Args {
     const PrecDesc *prec;
@@ -1297,9 +1290,6 @@ void GpuEncoder::t2_size_launch(const Plan &plan, bool with_kc, const int *halt,
     ra.budget = (int64_t *)budget.ptr;
     ra.out_rs = out_rs;
     ra.out_sum = out_rs ? (T2Summary *)(out_rs + 1) : nullptr;
-#ifndef JP2HIP_REPEAT_STAGE
-#define JP2HIP_REPEAT_STAGE 0  // stage-cost experiments only (kernels.hip)
-#endif
     T2TotalArgs ta;
     ta.nblocks = nb;
     ta.lengths = (const int32_t *)lengths.ptr;
@@ -1313,7 +1303,7 @@ void GpuEncoder::t2_size_launch(const Plan &plan, bool with_kc, const int *halt,
     ta.sum = (T2Summary *)t2sum.ptr;
     ta.rate = ra;
     ta.ticket = nullptr;
-    for (int rep_ = 0; rep_ < (JP2HIP_REPEAT_STAGE == 5 ? 2 : 1); rep_++) {
+    REPEAT_IF(5) {
         if (t2_nprec && t2_wave) {
             // the totals run in the last workgroup to finish (no k_t2_total launch)
             ta.ticket = (uint32_t *)t2ticket.ptr;
@@ -1330,18 +1320,18 @@ void GpuEncoder::t2_size_launch(const Plan &plan, bool with_kc, const int *halt,
 bool GpuEncoder::t2_size(const Plan &plan, bool with_kc, bool profile, StageTimes &st, T2Summary &sum,
                          std::string &err) {
     HIPCHECK(hipSetDevice(device));
-    HIPCHECK(hipEventRecord(ev[8], stream));
+    HIPCHECK(hipEventRecord(ev[kEvT2Begin], stream));
     t2_size_launch(plan, with_kc, nullptr);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipMemcpyAsync(h_sum, t2sum.ptr, sizeof(T2Summary), hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipEventRecord(ev[9], stream));
+    HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
     if (!host_wait(err)) return false;
     sum = *h_sum;
     if (profile) {
         float t;
-        HIPCHECK(hipEventElapsedTime(&t, ev[6], ev[7]));
+        HIPCHECK(hipEventElapsedTime(&t, ev[kEvSelectBegin], ev[kEvSelectEnd]));
         st.pcrd += t;
-        HIPCHECK(hipEventElapsedTime(&t, ev[8], ev[9]));
+        HIPCHECK(hipEventElapsedTime(&t, ev[kEvT2Begin], ev[kEvT2End]));
         st.t2 += t;
     }
     return true;
@@ -1359,7 +1349,7 @@ bool GpuEncoder::t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, u
     if (!ensure<uint8_t>(t2out, base + part_bytes, err)) return false;
     T2Args a = t2_args(plan);
     a.base = base;
-    HIPCHECK(hipEventRecord(ev[8], stream));
+    HIPCHECK(hipEventRecord(ev[kEvT2Begin], stream));
     if (t2_ntp) hipLaunchKernelGGL(k_t2_tp_emit, dim3((t2_ntp + 63) / 64), dim3(64), 0, stream, a);
     if (t2_nprec && t2_wave)
         hipLaunchKernelGGL(k_t2_wave<true>, dim3((t2_nprec + kT2Waves - 1) / kT2Waves), dim3(64 * kT2Waves),
@@ -1370,7 +1360,7 @@ bool GpuEncoder::t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, u
     HIPCHECK(hipGetLastError());
     // host_dst is pinned (api.cpp out_alloc)
 #if defined(JP2HIP_DIAG_NO_D2H)  // diagnostic builds only: the code-stream never leaves the GPU (output invalid)
-    HIPCHECK(hipEventRecord(ev[9], stream));
+    HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
     if (!host_wait(err)) return false;
     (void)host_dst;
 #elif !defined(JP2HIP_D2H_BLIT)
@@ -1378,21 +1368,21 @@ bool GpuEncoder::t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, u
         // on a DMA engine, released by the stream (dma_to_host): no blit
         // kernel competes with the other contexts' kernels for CUs
         if (!dma_to_host(host_dst, (const uint8_t *)t2out.ptr + base, part_bytes, err)) return false;
-        HIPCHECK(hipEventRecord(ev[9], stream));
+        HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
         if (profile && !host_wait(err)) return false;  // (the events below must be complete)
     } else {
-        HIPCHECK(hipEventRecord(ev[9], stream));
+        HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
         if (!host_wait(err)) return false;
     }
 #else  // A/B builds: the HIP runtime's copy (a blit kernel for pinned memory)
     if (part_bytes)
         HIPCHECK(hipMemcpyAsync(host_dst, (const uint8_t *)t2out.ptr + base, part_bytes, hipMemcpyDeviceToHost, stream));
-    HIPCHECK(hipEventRecord(ev[9], stream));
+    HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
     if (!host_wait(err)) return false;
 #endif
     if (profile) {
         float t;
-        HIPCHECK(hipEventElapsedTime(&t, ev[8], ev[9]));
+        HIPCHECK(hipEventElapsedTime(&t, ev[kEvT2Begin], ev[kEvT2End]));
         st.d2h += t;
     }
     return true;

@@ -151,7 +151,7 @@ def band_strips(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
 
     Returns (buffer, Layout, offsets) with offsets rebased to the buffer, so a
     rank uploads only its band of a multi-GB TIFF.  Offsets of strips outside
-    the band are 0 and never read (kernels.hip k_ingest / dwt.hip band_load
+    the band are 0 and never read (front.hip k_ingest / dwt.hip band_load
     touch only the rows of their band).  Compressed strips and tiles are
     packed whole, with their byte counts (the ``offsets`` array then holds
     the offsets followed by the counts, as jp2hip.tiff_layout returns them);

@@ -1,6 +1,7 @@
-// Host build of k_inflate (kernels.hip), for the CPU test suite: the kernel's
-// text is spliced in by tests/test_inflate_host.py between this file's shims
-// and main(), compiled with clang++ -fsanitize=address, and run on zlib
+// Host build of k_inflate (csrc/inflate_kernels.h), for the CPU test suite:
+// tests/test_inflate_host.py includes the kernel's header, and unpack_args.h
+// before it, between this file's shims and main(); the result is compiled
+// with clang++ -fsanitize=address, and run on zlib
 // streams (levels 0/1/6/9 at every byte alignment) and damaged streams.
 // [[SHIMS]]
 #include <cstdint>
