@@ -88,7 +88,10 @@ typedef struct jp2hip_recipe {
                              /* (test.jpx's order); <= 0: tile after tile      */
 } jp2hip_recipe;
 
-/* Where the samples live inside a source buffer (a baseline TIFF's strips). */
+/* Where the samples live inside a source buffer (a baseline TIFF's strips),
+ * and what the source says about them (extra_samples .. icc_bytes: carried
+ * into the JP2 / JPX file header, DESIGN.md "Source metadata"; all zero =
+ * a source that states nothing). */
 typedef struct jp2hip_layout {
     int32_t width, height, components, bits; /* bits 8 or 16, unsigned      */
     int32_t planar;                          /* 1 chunky, 2 planar          */
@@ -106,6 +109,18 @@ typedef struct jp2hip_layout {
     int32_t tile_width, tile_height;         /* tiled TIFF (0: strips): the */
                                              /* "strips" above are then the */
                                              /* tiles, row-major per plane  */
+    int32_t extra_samples;  /* 0: not stated (last of 2 or 4 channels is opacity,
+                               as before); else TIFF ExtraSamples value + 1:
+                               1 unspecified (no cdef box), 2 associated
+                               (premultiplied opacity), 3 unassociated opacity */
+    int32_t res_unit;       /* 0, 1: no resolution; 2 inch; 3 centimetre         */
+    uint32_t xres_num, xres_den, yres_num, yres_den; /* X/YResolution rationals:
+                               a res box is written when all four are non-zero
+                               and res_unit is 2 or 3                            */
+    const uint8_t *icc;     /* host pointer to the profile bytes (NULL: none);
+                               jp2hip_tiff_layout points it into `tiff`; read
+                               during the encode call only                       */
+    uint64_t icc_bytes;
 } jp2hip_layout;
 
 /* Stage times (ingest_ms .. t2_ms, t1_cm_ms, t1_mq_ms) come from HIP events
@@ -222,9 +237,27 @@ int jp2hip_encode_tiff(jp2hip_ctx *ctx, const uint8_t *tiff, size_t len, int con
  * `offsets` receives 2 * nstrips entries: the strip offsets, then their byte
  * counts (layout->strip_bytes points at the second half).  Tiled TIFFs
  * (TileWidth/TileLength) are described the same way, one entry per tile,
- * and always carry the byte counts; they are untiled in HBM before ingest. */
+ * and always carry the byte counts; they are untiled in HBM before ingest.
+ * The metadata fields come from ICCProfile (34675; layout->icc points into
+ * `tiff`, so it lives as long as that buffer), ExtraSamples (338),
+ * X/YResolution (282, 283) and ResolutionUnit (296); a malformed or
+ * out-of-range metadata tag counts as absent and never fails the parse. */
 int jp2hip_tiff_layout(const uint8_t *tiff, size_t len, jp2hip_layout *layout,
                        uint64_t *offsets, int32_t max_offsets);
+
+/* The bytes that precede the code-stream (signature .. jp2c box header) for
+ * this source description, format and code-stream length.  Returns their
+ * count (0 for JP2HIP_FORMAT_J2K) and writes them when cap suffices; < 0 on
+ * a null argument.  Reads only width/height/components/bits and the metadata
+ * fields of the layout; no strips, no context, no device.
+ *   colr: no (usable) ICC profile -> enumerated sRGB / greyscale; a matrix /
+ *     TRC input or display profile -> METH 2 with the profile; any other
+ *     profile -> JPX: the enumerated box, then METH 3 with the profile
+ *     (a JP2 reader takes the first box); JP2: the enumerated box alone.
+ *   cdef: by extra_samples (above), for 2 or 4 channels.
+ *   res : one resc box (capture resolution, points per metre). */
+int64_t jp2hip_file_header(const jp2hip_layout *layout, int32_t format,
+                           uint64_t codestream_bytes, uint8_t *dst, size_t cap);
 
 /* Device-resident source: d_src holds the TIFF file (or any buffer the
  * layout describes) in HBM.  This is the entry the benchmark times. */
@@ -274,7 +307,9 @@ void jp2hip_split_rows(int32_t height, int32_t tile_h, int32_t flush_period, int
  * headers, the last rank's ends with EOC.  d_src/layout describe the whole
  * TIFF, but only the strips of this rank's rows are read, so d_src may hold
  * just those (with strip offsets relative to it).  Collective: every rank
- * must call it with the same image geometry and recipe. */
+ * must call it with the same image geometry, recipe and source metadata
+ * (extra_samples .. icc_bytes, the profile's bytes included; rank 0 sizes
+ * and writes the file header from its own layout). */
 int jp2hip_encode_device_split(jp2hip_ctx *ctx, const void *d_src, size_t src_len,
                                const jp2hip_layout *layout, int conversion,
                                const jp2hip_recipe *recipe, const jp2hip_split *split,

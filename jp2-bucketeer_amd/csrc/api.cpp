@@ -236,6 +236,26 @@ struct TiffReader {
         const size_t at = (size_t)(base + (uint64_t)sz * i);
         return sz == 2 ? u16(at) : (sz == 4 ? u32(at) : (sz == 8 ? u64(at) : (at < n ? b[at] : 0)));
     }
+    // Metadata tags (ICC profile, ExtraSamples, resolution): where the
+    // entry's `cnt` values of `sz` bytes lie, or false when they do not lie
+    // inside the file -- such a tag counts as absent, it never fails the parse.
+    bool data_at(size_t e, uint32_t sz, uint64_t cnt, size_t &at) const {
+        const size_t inl = big ? 8 : 4, voff = big ? e + 12 : e + 8;
+        if (cnt == 0 || cnt > n / sz) return false;
+        const uint64_t bytes = (uint64_t)sz * cnt;
+        const uint64_t base = bytes <= inl ? voff : (big ? u64(voff) : u32(voff));
+        if (base > n || bytes > n - base) return false;
+        at = (size_t)base;
+        return true;
+    }
+    // the first value of a RATIONAL entry (two LONGs: numerator, denominator)
+    bool rational(size_t e, uint32_t &num, uint32_t &den) const {
+        size_t at;
+        if (u16(e + 2) != 5 || !data_at(e, 8, count(e), at)) return false;
+        num = u32(at);
+        den = u32(at + 4);
+        return true;
+    }
 };
 
 int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<uint64_t> &offs) {
@@ -262,6 +282,13 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
     uint32_t photo = 0xFFFFFFFFu;  // absent: inferred from SamplesPerPixel
     size_t e_off = 0, e_cnt = 0;
     uint32_t n_off = 0, tw = 0, th = 0;
+    // what the file states about its pixels (the JP2 / JPX header carries it):
+    // a malformed one of these tags is an absent one
+    int32_t extra = 0;       // ExtraSamples value + 1; 0 absent
+    uint32_t res_unit = 2;   // ResolutionUnit: inch when absent
+    uint32_t xr[2] = {0, 0}, yr[2] = {0, 0};
+    const uint8_t *icc = nullptr;
+    uint64_t icc_bytes = 0;
     if (ne > (len - ifd - ifd_hdr) / t.entry_size()) return fail("tiff: truncated IFD");
     for (uint64_t i = 0; i < ne; i++) {
         size_t e = ifd + ifd_hdr + t.entry_size() * (size_t)i;
@@ -282,6 +309,30 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
         case 324: e_off = e; n_off = (uint32_t)std::min<uint64_t>(t.count(e), 0xFFFFFFFFu); break;  // TileOffsets
         case 325: e_cnt = e; break;                                                                  // TileByteCounts
         case 339: fmt = (uint32_t)t.val(e, 0); break;
+        case 282: if (!t.rational(e, xr[0], xr[1])) xr[0] = xr[1] = 0; break;  // XResolution
+        case 283: if (!t.rational(e, yr[0], yr[1])) yr[0] = yr[1] = 0; break;  // YResolution
+        case 296: {                                                            // ResolutionUnit
+            size_t at;
+            res_unit = (t.u16(e + 2) == 3 && t.data_at(e, 2, t.count(e), at)) ? t.u16(at) : 0;
+            break;
+        }
+        case 338: {  // ExtraSamples: the first value; an unknown one reads as 0 (unspecified)
+            size_t at;
+            extra = 0;
+            if (t.u16(e + 2) == 3 && t.data_at(e, 2, t.count(e), at)) extra = 1 + (int32_t)(t.u16(at) <= 2 ? t.u16(at) : 0);
+            break;
+        }
+        case 34675: {  // ICCProfile: recorded raw, classified when the header is written
+            size_t at;
+            const uint32_t type = t.u16(e + 2);
+            icc = nullptr;
+            icc_bytes = 0;
+            if ((type == 7 || type == 1) && t.data_at(e, 1, t.count(e), at)) {
+                icc = buf + at;
+                icc_bytes = t.count(e);
+            }
+            break;
+        }
         default: break;
         }
     }
@@ -351,6 +402,17 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
     lay->strip_bytes = packed ? offs.data() + need : nullptr;
     lay->tile_width = (int32_t)tw;
     lay->tile_height = (int32_t)th;
+    // a resolution needs both rationals whole and a unit (1 "none" is kept
+    // as stated; the header writes a res box for inch and centimetre only)
+    const bool res = xr[0] && xr[1] && yr[0] && yr[1] && res_unit >= 1 && res_unit <= 3;
+    lay->extra_samples = extra;
+    lay->res_unit = res ? (int32_t)res_unit : 0;
+    lay->xres_num = res ? xr[0] : 0;
+    lay->xres_den = res ? xr[1] : 0;
+    lay->yres_num = res ? yr[0] : 0;
+    lay->yres_den = res ? yr[1] : 0;
+    lay->icc = icc;
+    lay->icc_bytes = icc_bytes;
     return 0;
 }
 
@@ -601,6 +663,9 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         return fail("conversion must be JP2HIP_LOSSY (0) or JP2HIP_LOSSLESS (1)");
     const jp2hip_recipe rc = recipe_of(recipe, conversion);
     if (!lay || !d_src) return fail("null source or layout");
+    // what the source states about its pixels: into the file header, per
+    // encode (the cached plan below is shared by files that differ in it)
+    const SourceMeta meta = source_meta(*lay);
     ctx->gpu.take_waits();  // count this encode's host waits (stats)
     ctx->gpu.begin_encode();
     EncodeEnd end{ctx};
@@ -700,11 +765,11 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     std::vector<int64_t> layer_end((size_t)L);
     layer_end_of(plan, sum.tp_hdr_bytes, sum.layer_bytes, layer_end.data());
     main_header(plan, mh, K.data(), layer_end.data());
-    const size_t fh = file_header_bytes(plan);
+    const size_t fh = file_header_bytes(plan, meta);
     const size_t n = fh + (size_t)cs_bytes;
     uint8_t *buf = out_alloc(n);
     if (!buf) return fail("out of (pinned) host memory");
-    write_file_header(plan, (uint64_t)cs_bytes, buf);
+    write_file_header(plan, meta, (uint64_t)cs_bytes, buf);
     std::memcpy(buf + fh, mh.data(), mh.size());
     if (!ctx->gpu.t2_emit(plan, 0, (uint64_t)sum.part_bytes, buf + fh + mh.size(), prof, st, err) ||
         !ctx->gpu.collect_profile(st, err)) {
@@ -744,6 +809,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     };
     const jp2hip_recipe rc = recipe_of(recipe, conversion);
     if (!lay || !d_src) return fail("null source or layout");
+    const SourceMeta meta = source_meta(*lay);  // rank 0's file header; equal on all ranks (jp2hip.h)
     ctx->gpu.take_waits();
     ctx->gpu.begin_encode();
     EncodeEnd end{ctx};
@@ -898,7 +964,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     }
     // this rank's part of the file
     const bool with_main = rank == 0, with_eoc = rank == world - 1;
-    const size_t fh = with_main ? file_header_bytes(full) : 0;
+    const size_t fh = with_main ? file_header_bytes(full, meta) : 0;
     const uint64_t head = with_main ? fh + mh.size() : 0;
     const uint64_t part = head + (uint64_t)(have ? sum.part_bytes : 0) + (with_eoc ? 2 : 0);
     // everything this rank's emission allocates is allocated before the
@@ -932,7 +998,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         std::vector<int64_t> layer_end((size_t)L);
         layer_end_of(full, g_tp_hdr, g_layer.data(), layer_end.data());
         main_header(full, mh, Kcom.data(), layer_end.data());
-        write_file_header(full, (uint64_t)cs_bytes, buf);
+        write_file_header(full, meta, (uint64_t)cs_bytes, buf);
         std::memcpy(buf + fh, mh.data(), mh.size());
     }
     if (have && (!ctx->gpu.t2_emit(sub, 0, (uint64_t)sum.part_bytes, buf + head, prof, st, err) ||
@@ -1395,6 +1461,25 @@ int jp2hip_tiff_layout(const uint8_t *tiff, size_t len, jp2hip_layout *layout, u
     layout->strip_offsets = offsets;
     layout->strip_bytes = (layout->compression > 1 || layout->tile_width > 0) ? offsets + layout->nstrips : nullptr;
     return 0;
+}
+
+int64_t jp2hip_file_header(const jp2hip_layout *layout, int32_t format, uint64_t codestream_bytes, uint8_t *dst,
+                           size_t cap) {
+    if (!layout) return fail("null layout");
+    if (format != JP2HIP_FORMAT_J2K && format != JP2HIP_FORMAT_JP2 && format != JP2HIP_FORMAT_JPX)
+        return fail("format must be JP2HIP_FORMAT_J2K, _JP2 or _JPX");
+    // the two functions the encodes call, on a plan that holds what they read
+    jp2hip::Plan hdr;
+    std::memset(&hdr.rc, 0, sizeof hdr.rc);
+    hdr.rc.format = format;
+    hdr.w = layout->width;
+    hdr.h = layout->height;
+    hdr.nc = layout->components;
+    hdr.bits = layout->bits;
+    const jp2hip::SourceMeta meta = jp2hip::source_meta(*layout);
+    const size_t n = jp2hip::file_header_bytes(hdr, meta);
+    if (n && dst && cap >= n) jp2hip::write_file_header(hdr, meta, codestream_bytes, dst);
+    return (int64_t)n;
 }
 
 int jp2hip_encode_device(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *layout,

@@ -201,8 +201,25 @@ struct RateState {
 // the length does not depend on them).
 void main_header(const Plan &P, std::vector<uint8_t> &v, const uint64_t *K, const int64_t *layer_end);
 
-// JP2 / JPX boxes in front of the code-stream (0 bytes for raw J2K).
-size_t file_header_bytes(const Plan &plan);
-void write_file_header(const Plan &plan, uint64_t cs_bytes, uint8_t *dst);
+// What the source file states about its pixels (jp2hip_layout's metadata
+// fields): it differs from file to file, so it is passed per encode and is
+// never part of a cached Plan.  `icc` is the caller's host memory.
+struct SourceMeta {
+    int32_t extra_samples = 0, res_unit = 0;
+    uint32_t xres_num = 0, xres_den = 0, yres_num = 0, yres_den = 0;
+    const uint8_t *icc = nullptr;
+    uint64_t icc_bytes = 0;
+};
+SourceMeta source_meta(const jp2hip_layout &lay);
+
+// An ICC profile for an image of `nc` channels: 0 unusable, 1 restricted
+// (matrix / TRC input or display profile: JP2 METH 2), 2 any other usable
+// profile (JPX METH 3); *embed = the bytes to embed (the profile's own size).
+int classify_icc(const uint8_t *icc, uint64_t n, int nc, uint32_t *embed);
+
+// JP2 / JPX boxes in front of the code-stream (0 bytes for raw J2K); only
+// plan.rc.format, w, h, nc and bits are read.
+size_t file_header_bytes(const Plan &plan, const SourceMeta &meta);
+void write_file_header(const Plan &plan, const SourceMeta &meta, uint64_t cs_bytes, uint8_t *dst);
 
 }  // namespace jp2hip

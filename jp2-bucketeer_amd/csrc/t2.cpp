@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 
 #include "jp2hip_internal.h"
 
@@ -176,17 +177,142 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
     }
 }
 
-size_t file_header_bytes(const Plan &P) {
-    if (P.rc.format == JP2HIP_FORMAT_J2K) return 0;
+// ---- the boxes in front of the code-stream ----
+// What the source states about its pixels goes into jp2h (DESIGN.md "Source
+// metadata"): its ICC profile into colr, its ExtraSamples into cdef, its
+// resolution into res.  A source that states nothing (SourceMeta all zero)
+// gets the header the oracle writes (write_file_header there).
+
+SourceMeta source_meta(const jp2hip_layout &lay) {
+    SourceMeta m;
+    m.extra_samples = lay.extra_samples;
+    m.res_unit = lay.res_unit;
+    m.xres_num = lay.xres_num; m.xres_den = lay.xres_den;
+    m.yres_num = lay.yres_num; m.yres_den = lay.yres_den;
+    if (lay.icc && lay.icc_bytes) { m.icc = lay.icc; m.icc_bytes = lay.icc_bytes; }
+    return m;
+}
+
+namespace {
+
+inline uint32_t rd32(const uint8_t *p) {
+    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+}
+inline bool sig_is(const uint8_t *p, const char *s) { return std::memcmp(p, s, 4) == 0; }
+
+// a profile this long would not leave jp2h's 32-bit box length room for the rest
+constexpr uint64_t kMaxIccBytes = 0xFFFFFFFFull - 1024;
+
+struct Resc {
+    uint32_t n = 0, d = 0;
+    int e = 0;
+};
+
+// One axis of the capture resolution in points per metre, as resc stores it
+// (N / D * 10^E, N and D 16 bits).  The value is the exact ratio P / Q; when
+// the reduced P and Q fit they are stored as they are, else D = 1 and N is
+// the value rounded (half up) to the most digits 16 bits hold: 6553.5 <=
+// v / 10^E < 65535.5, a relative error of at most 0.5 / 6553.5.  (E stays
+// within -13..9 for 32-bit rationals, far inside resc's int8.)
+bool resc_axis(uint32_t num, uint32_t den, int unit, Resc &r) {
+    if (!num || !den || (unit != 2 && unit != 3)) return false;
+    uint64_t P = (uint64_t)num * (unit == 2 ? 10000 : 100), Q = (uint64_t)den * (unit == 2 ? 254 : 1);
+    const uint64_t g = std::gcd(P, Q);
+    P /= g;
+    Q /= g;
+    if (P <= 65535 && Q <= 65535) {
+        r.n = (uint32_t)P; r.d = (uint32_t)Q; r.e = 0;
+        return true;
+    }
+    typedef unsigned __int128 u128;
+    for (int E = -20; E <= 20; E++) {  // the smallest E whose N fits: the one of the rule above
+        u128 A = P, B = Q;             // A / B = v / 10^E
+        for (int k = 0; k < (E < 0 ? -E : E); k++) (E < 0 ? A : B) *= 10;
+        const u128 N = (2 * A + B) / (2 * B);
+        if (N > 65535) continue;
+        if (N < 6554) return false;  // (not reached: E - 1 gave N > 65535)
+        r.n = (uint32_t)N; r.d = 1; r.e = E;
+        return true;
+    }
+    return false;
+}
+
+// Which boxes jp2h holds for this image and source, and its length.
+struct HeaderBoxes {
+    bool enum_colr = true;   // the 15-byte enumerated colr box
+    int meth = 0;            // 2 / 3: a colr box with the profile follows; 0: none
+    uint32_t icc_len = 0;
+    int cdef_typ = -1;       // Typ of the last channel; -1: no cdef box
+    bool res = false;
+    Resc v, h;
+    uint32_t jp2h = 0;
+};
+
+HeaderBoxes header_boxes(const Plan &P, const SourceMeta &m) {
+    HeaderBoxes b;
     const int nc = P.nc;
-    const bool cdef = (nc == 4 || nc == 2);
+    uint32_t embed = 0;
+    const int cls = classify_icc(m.icc, m.icc_bytes, nc, &embed);
+    if (cls == 1) {
+        b.enum_colr = false;
+        b.meth = 2;
+    } else if (cls == 2 && P.rc.format == JP2HIP_FORMAT_JPX) {
+        b.meth = 3;  // after the enumerated box: a JP2 reader uses the first colr
+    }
+    b.icc_len = b.meth ? embed : 0;
+    if (nc == 4 || nc == 2) {
+        // ExtraSamples + 1: 1 unspecified (the channel is not opacity: no
+        // cdef), 2 associated = premultiplied opacity, 3 unassociated; 0 (or
+        // anything else): not stated, the last channel is opacity
+        b.cdef_typ = m.extra_samples == 1 ? -1 : (m.extra_samples == 2 ? 2 : 1);
+    }
+    b.res = resc_axis(m.yres_num, m.yres_den, m.res_unit, b.v) && resc_axis(m.xres_num, m.xres_den, m.res_unit, b.h);
+    b.jp2h = 8 + (8 + 14) + (b.enum_colr ? 8 + 7 : 0) + (b.meth ? 8 + 3 + b.icc_len : 0) +
+             (b.cdef_typ >= 0 ? (uint32_t)(8 + 2 + 6 * nc) : 0) + (b.res ? 8 + (8 + 10) : 0);
+    return b;
+}
+
+}  // namespace
+
+int classify_icc(const uint8_t *icc, uint64_t n, int nc, uint32_t *embed) {
+    *embed = 0;
+    if (!icc || n < 132) return 0;
+    const uint64_t S = rd32(icc);  // the profile's own size: what is embedded
+    if (S < 132 || S > n || S > kMaxIccBytes) return 0;
+    if (!sig_is(icc + 36, "acsp")) return 0;
+    const bool rgb = nc >= 3;
+    if (!sig_is(icc + 16, rgb ? "RGB " : "GRAY")) return 0;
+    *embed = (uint32_t)S;
+    // restricted (15444-1 I.5.3.3 METH 2): a matrix / TRC input profile; display
+    // class counts too -- the working spaces masters carry (sRGB, Adobe RGB,
+    // eciRGB, ProPhoto) are mntr matrix / TRC profiles and JP2 readers take them
+    if (!sig_is(icc + 12, "scnr") && !sig_is(icc + 12, "mntr")) return 2;
+    if (!sig_is(icc + 20, "XYZ ")) return 2;
+    const uint64_t ntags = rd32(icc + 128);
+    if (132 + 12 * ntags > S) return 2;
+    static const char *const kRgbTags[] = {"rXYZ", "gXYZ", "bXYZ", "rTRC", "gTRC", "bTRC"};
+    static const char *const kGrayTags[] = {"kTRC"};
+    const char *const *need = rgb ? kRgbTags : kGrayTags;
+    const int nneed = rgb ? 6 : 1;
+    unsigned have = 0;
+    for (uint64_t i = 0; i < ntags; i++) {
+        const uint8_t *t = icc + 132 + 12 * i;
+        if (sig_is(t, "A2B0")) return 2;
+        for (int k = 0; k < nneed; k++)
+            if (sig_is(t, need[k])) have |= 1u << k;
+    }
+    return have == (1u << nneed) - 1 ? 1 : 2;
+}
+
+size_t file_header_bytes(const Plan &P, const SourceMeta &meta) {
+    if (P.rc.format == JP2HIP_FORMAT_J2K) return 0;
     size_t n = 12;                                                                    // signature
     n += (P.rc.format == JP2HIP_FORMAT_JPX) ? (8 + 4 + 4 + 12) + (8 + 10) : (8 + 4 + 4 + 4);  // ftyp (+rreq)
-    n += 8 + (8 + 14) + (8 + 7) + (cdef ? (size_t)(8 + 2 + 6 * nc) : 0);             // jp2h
+    n += header_boxes(P, meta).jp2h;
     return n + 8;                                                                     // jp2c box header
 }
 
-void write_file_header(const Plan &P, uint64_t cs_bytes, uint8_t *dst) {
+void write_file_header(const Plan &P, const SourceMeta &meta, uint64_t cs_bytes, uint8_t *dst) {
     if (P.rc.format == JP2HIP_FORMAT_J2K) return;
     uint8_t *p = dst;
     auto raw = [&](const void *s, size_t n) { std::memcpy(p, s, n); p += n; };
@@ -209,22 +335,36 @@ void write_file_header(const Plan &P, uint64_t cs_bytes, uint8_t *dst) {
         box(8 + 4 + 4 + 4, "ftyp");
         raw("jp2 ", 4); u32(0); raw("jp2 ", 4);
     }
-    const bool cdef = (nc == 4 || nc == 2);
-    const uint32_t ihdr = 8 + 14, colr = 8 + 7, cdefl = cdef ? (uint32_t)(8 + 2 + 6 * nc) : 0;
-    box(8 + ihdr + colr + cdefl, "jp2h");
-    box(ihdr, "ihdr");
+    const HeaderBoxes hb = header_boxes(P, meta);
+    box(hb.jp2h, "jp2h");
+    box(8 + 14, "ihdr");
     u32((uint32_t)P.h); u32((uint32_t)P.w);
     u16(nc); u8(P.bits - 1); u8(7); u8(0); u8(0);
-    box(colr, "colr");
-    u8(1); u8(0); u8(0);
-    u32(nc >= 3 ? 16 : 17);  // sRGB / greyscale
-    if (cdef) {
-        box(cdefl, "cdef");
+    if (hb.enum_colr) {
+        box(8 + 7, "colr");
+        u8(1); u8(0); u8(0);
+        u32(nc >= 3 ? 16 : 17);  // sRGB / greyscale
+    }
+    if (hb.meth) {
+        box(8 + 3 + hb.icc_len, "colr");
+        u8(hb.meth);
+        u8(hb.meth == 3 ? 1 : 0);  // PREC: above the enumerated box's 0
+        u8(hb.meth == 3 ? 1 : 0);  // APPROX (JPX): accurate
+        raw(meta.icc, hb.icc_len);
+    }
+    if (hb.cdef_typ >= 0) {
+        box((uint32_t)(8 + 2 + 6 * nc), "cdef");
         u16(nc);
         for (int c = 0; c < nc; c++) {
             const bool alpha = (c == nc - 1);
-            u16(c); u16(alpha ? 1 : 0); u16(alpha ? 0 : c + 1);
+            u16(c); u16(alpha ? hb.cdef_typ : 0); u16(alpha ? 0 : c + 1);
         }
+    }
+    if (hb.res) {
+        box(8 + (8 + 10), "res ");
+        box(8 + 10, "resc");  // capture resolution; vertical first
+        u16((int)hb.v.n); u16((int)hb.v.d); u16((int)hb.h.n); u16((int)hb.h.d);
+        u8(hb.v.e); u8(hb.h.e);
     }
     // a code-stream past 4 GiB: length 0 = "to the end of the file" (last box)
     box(8 + cs_bytes > 0xFFFFFFFFull ? 0u : (uint32_t)(8 + cs_bytes), "jp2c");

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import (CFUNCTYPE, POINTER, Structure, byref, c_char_p, c_double, c_int, c_int32,
-                    c_int64, c_size_t, c_uint8, c_uint64, c_void_p)
+                    c_int64, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JP2HIP_LIBRARY") or os.path.join(HERE, "libjp2hip.so")  # override: experiments only
@@ -46,7 +46,31 @@ class Layout(Structure):
                 ("strip_offsets", POINTER(c_uint64)),
                 ("compression", c_int32), ("predictor", c_int32),
                 ("strip_bytes", POINTER(c_uint64)),
-                ("tile_width", c_int32), ("tile_height", c_int32)]
+                ("tile_width", c_int32), ("tile_height", c_int32),
+                # what the source states about its pixels (zero: nothing), carried
+                # into the JP2 / JPX header
+                ("extra_samples", c_int32), ("res_unit", c_int32),
+                ("xres_num", c_uint32), ("xres_den", c_uint32),
+                ("yres_num", c_uint32), ("yres_den", c_uint32),
+                ("icc", POINTER(c_uint8)), ("icc_bytes", c_uint64)]
+
+    METADATA = ("extra_samples", "res_unit", "xres_num", "xres_den", "yres_num", "yres_den")
+
+    def icc_profile(self) -> bytes:
+        """The ICC profile bytes the layout points at (b"" when it has none)."""
+        return ctypes.string_at(self.icc, self.icc_bytes) if self.icc and self.icc_bytes else b""
+
+    def set_icc_profile(self, profile: bytes) -> None:
+        """Point the layout at a copy of `profile` that lives as long as it does."""
+        self._icc_keep = (c_uint8 * max(1, len(profile))).from_buffer_copy(profile or b"\0")
+        self.icc = ctypes.cast(self._icc_keep, POINTER(c_uint8)) if profile else None
+        self.icc_bytes = len(profile)
+
+    def copy_metadata(self, src: "Layout") -> None:
+        """Take `src`'s metadata fields (a band's layout keeps the file's)."""
+        for name in Layout.METADATA:
+            setattr(self, name, getattr(src, name))
+        self.set_icc_profile(src.icc_profile())
 
 
 class Stats(Structure):
@@ -67,7 +91,7 @@ class Stats(Structure):
 EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device_count", "jp2hip_device_ordinals",
            "jp2hip_recipe_init",
            "jp2hip_create", "jp2hip_destroy", "jp2hip_encode_file", "jp2hip_encode_tiff",
-           "jp2hip_tiff_layout", "jp2hip_encode_device", "jp2hip_free",
+           "jp2hip_tiff_layout", "jp2hip_file_header", "jp2hip_encode_device", "jp2hip_free",
            # batch path (csrc/batch.cpp; bound in jp2hip.batch)
            "jp2hip_batch_create", "jp2hip_batch_submit", "jp2hip_batch_wait", "jp2hip_batch_pending",
            "jp2hip_batch_destroy",
@@ -112,6 +136,8 @@ def lib():
                                      POINTER(POINTER(c_uint8)), POINTER(c_size_t), POINTER(Stats)]
     L.jp2hip_tiff_layout.argtypes = [c_void_p, c_size_t, POINTER(Layout), POINTER(c_uint64),
                                      c_int32]
+    L.jp2hip_file_header.argtypes = [POINTER(Layout), c_int32, c_uint64, c_void_p, c_size_t]
+    L.jp2hip_file_header.restype = c_int64
     L.jp2hip_encode_device.argtypes = [c_void_p, c_void_p, c_size_t, POINTER(Layout), c_int,
                                        POINTER(Recipe), POINTER(POINTER(c_uint8)),
                                        POINTER(c_size_t), POINTER(Stats)]
@@ -218,7 +244,8 @@ def recipe(conversion: int, **overrides) -> Recipe:
 
 
 def tiff_layout(data: bytes):
-    """Parse a baseline TIFF header; returns (Layout, offsets array)."""
+    """Parse a baseline TIFF header; returns (Layout, offsets array).  The
+    Layout owns a copy of the file's ICC profile (Layout.icc points at it)."""
     lay = Layout()
     cap = 1 << 20
     offs = (c_uint64 * cap)()
@@ -232,7 +259,23 @@ def tiff_layout(data: bytes):
     lay.strip_offsets = ctypes.cast(keep, POINTER(c_uint64))
     if packed:
         lay.strip_bytes = ctypes.cast(ctypes.byref(keep, 8 * n), POINTER(c_uint64))
+    # the library pointed lay.icc into `buf`, a temporary: re-point it at a
+    # copy the Layout keeps
+    lay.set_icc_profile(lay.icc_profile())
     return lay, keep
+
+
+def file_header(layout: Layout, fmt: int, codestream_bytes: int) -> bytes:
+    """The bytes in front of the code-stream (signature .. jp2c box header)
+    for this source description (jp2hip_file_header; no GPU): b"" for
+    FORMAT_J2K."""
+    n = int(lib().jp2hip_file_header(byref(layout), fmt, codestream_bytes, None, 0))
+    if n < 0:
+        raise Jp2hipError(last_error())
+    out = ctypes.create_string_buffer(max(1, n))
+    if int(lib().jp2hip_file_header(byref(layout), fmt, codestream_bytes, out, n)) != n:
+        raise Jp2hipError(last_error())
+    return out.raw[:n]
 
 
 class _PinnedBuffer:

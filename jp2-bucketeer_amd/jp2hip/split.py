@@ -176,6 +176,7 @@ def band_strips(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
     lay = Layout(layout.width, layout.height, layout.components, layout.bits, layout.planar,
                  layout.big_endian, layout.rows_per_strip, layout.nstrips,
                  ctypes.cast(new, POINTER(c_uint64)))
+    lay.copy_metadata(layout)  # equal on every rank; rank 0 writes the file header from it
     return b"".join(chunks), lay, new
 
 
@@ -204,6 +205,7 @@ def _band_units(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
                  layout.big_endian, layout.rows_per_strip, n, ctypes.cast(new, POINTER(c_uint64)),
                  layout.compression, layout.predictor, ctypes.cast(ctypes.byref(new, 8 * n), POINTER(c_uint64)),
                  layout.tile_width, layout.tile_height)
+    lay.copy_metadata(layout)
     return b"".join(chunks), lay, new
 
 
