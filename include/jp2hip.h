@@ -88,12 +88,26 @@ typedef struct jp2hip_recipe {
                              /* (test.jpx's order); <= 0: tile after tile      */
 } jp2hip_recipe;
 
+#define JP2HIP_PHOTO_DEFAULT 0       /* BlackIsZero grey / RGB, by component count */
+#define JP2HIP_PHOTO_WHITE_IS_ZERO 1 /* grey, 0 = white (bits 1, 2, 4 only)        */
+#define JP2HIP_PHOTO_PALETTE 2       /* indices into `colormap` (bits 1, 2, 4, 8)  */
+
 /* Where the samples live inside a source buffer (a baseline TIFF's strips),
  * and what the source says about them (extra_samples .. icc_bytes: carried
  * into the JP2 / JPX file header, DESIGN.md "Source metadata"; all zero =
- * a source that states nothing). */
+ * a source that states nothing).
+ * components and bits describe the source.  Samples of 1, 2 or 4 bits (one
+ * component; rows packed MSB-first unless fill_order is 2, each row -- of the
+ * image for strips, of a tile for tiles -- starting on a byte boundary) and
+ * palette indices are expanded to 8-bit samples in HBM before ingest
+ * (DESIGN.md "S1b sample expansion"): value v of `bits` bits becomes
+ * v * 255 / (2^bits - 1), WhiteIsZero then 255 minus that, and a palette
+ * index becomes three components (R, G, B).  jp2hip_encoded_format() names
+ * what the code-stream carries.  The fields from `photometric` on were
+ * appended: all zero means a layout as it was before them. */
 typedef struct jp2hip_layout {
-    int32_t width, height, components, bits; /* bits 8 or 16, unsigned      */
+    int32_t width, height, components, bits; /* bits 8 or 16, unsigned; also*/
+                                             /* 1, 2, 4 (one component)     */
     int32_t planar;                          /* 1 chunky, 2 planar          */
     int32_t big_endian;                      /* 16-bit sample byte order    */
     int32_t rows_per_strip;
@@ -121,6 +135,18 @@ typedef struct jp2hip_layout {
                                jp2hip_tiff_layout points it into `tiff`; read
                                during the encode call only                       */
     uint64_t icc_bytes;
+    int32_t photometric;    /* JP2HIP_PHOTO_*                                    */
+    int32_t fill_order;     /* TIFF FillOrder for bits < 8: 0, 1 the first pixel
+                               of a byte is in its high bits; 2 in its low bits  */
+    const uint8_t *colormap; /* JP2HIP_PHOTO_PALETTE: the ColorMap tag's data as
+                               the file holds it -- 3 * 2^bits 16-bit values in
+                               the byte order `big_endian` names, every red, then
+                               every green, then every blue; a component is the
+                               entry >> 8, or the entry itself when no entry of
+                               the map exceeds 255.  A host pointer like `icc`:
+                               jp2hip_tiff_layout points it into `tiff`; read
+                               during the encode call only                       */
+    uint64_t colormap_entries; /* 3 * 2^bits                                     */
 } jp2hip_layout;
 
 /* Stage times (ingest_ms .. t2_ms, t1_cm_ms, t1_mq_ms) come from HIP events
@@ -129,7 +155,9 @@ typedef struct jp2hip_layout {
 typedef struct jp2hip_stats {
     double total_ms;      /* host wall time of the call                       */
     double h2d_ms;        /* source upload (encode_file / encode_tiff only)   */
-    double ingest_ms;     /* strip gather + level shift + RCT/ICT kernel      */
+    double ingest_ms;     /* sample expansion (k_expand: sub-byte / palette   */
+                          /* sources only); the strip gather itself is part   */
+                          /* of dwt_ms (fused into the first DWT level)       */
     double dwt_ms;        /* all DWT kernels                                  */
     double quant_ms;      /* quantisation + bit-plane kernel                  */
     double t1_ms;         /* EBCOT tier-1 kernels                             */
@@ -241,15 +269,30 @@ int jp2hip_encode_tiff(jp2hip_ctx *ctx, const uint8_t *tiff, size_t len, int con
  * The metadata fields come from ICCProfile (34675; layout->icc points into
  * `tiff`, so it lives as long as that buffer), ExtraSamples (338),
  * X/YResolution (282, 283) and ResolutionUnit (296); a malformed or
- * out-of-range metadata tag counts as absent and never fails the parse. */
+ * out-of-range metadata tag counts as absent and never fails the parse.
+ * Pixel formats: 8- and 16-bit BlackIsZero grey and RGB (with or without an
+ * extra sample); 1-, 2- and 4-bit grey, BlackIsZero or WhiteIsZero, in
+ * either FillOrder (266); palette colour (PhotometricInterpretation 3) of
+ * 1, 2, 4 or 8 bits with a ColorMap (320) of exactly 3 * 2^bits SHORTs that
+ * lies inside the file (layout->colormap points into `tiff`).  Refused, each
+ * with its own message: sub-byte samples with more than one sample per
+ * pixel, other bit depths, Predictor 2 below 8 bits, a palette without a
+ * (whole) ColorMap or with 16-bit indices, 8- and 16-bit WhiteIsZero, CMYK,
+ * YCbCr, Lab, JPEG and CCITT compression. */
 int jp2hip_tiff_layout(const uint8_t *tiff, size_t len, jp2hip_layout *layout,
                        uint64_t *offsets, int32_t max_offsets);
+
+/* What the code-stream of this source carries: 3 components of 8 bits for a
+ * palette, 1 of 8 bits for 1-, 2- and 4-bit grey, else the layout's own
+ * components and bits.  Returns 0, or < 0 on a null argument. */
+int jp2hip_encoded_format(const jp2hip_layout *layout, int32_t *components, int32_t *bits);
 
 /* The bytes that precede the code-stream (signature .. jp2c box header) for
  * this source description, format and code-stream length.  Returns their
  * count (0 for JP2HIP_FORMAT_J2K) and writes them when cap suffices; < 0 on
- * a null argument.  Reads only width/height/components/bits and the metadata
- * fields of the layout; no strips, no context, no device.
+ * a null argument.  Reads only width/height/components/bits, the pixel
+ * format (the header describes jp2hip_encoded_format's components and bits)
+ * and the metadata fields of the layout; no strips, no context, no device.
  *   colr: no (usable) ICC profile -> enumerated sRGB / greyscale; a matrix /
  *     TRC input or display profile -> METH 2 with the profile; any other
  *     profile -> JPX: the enumerated box, then METH 3 with the profile

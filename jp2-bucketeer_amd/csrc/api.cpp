@@ -258,6 +258,10 @@ struct TiffReader {
     }
 };
 
+// Bytes of a row of `w` pixels: rows start on byte boundaries, samples below
+// 8 bits are packed (TIFF 6.0 section 3 and 5).
+uint64_t packed_row_bytes(uint64_t w, uint64_t spp, uint64_t bits) { return (w * spp * bits + 7) / 8; }
+
 int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<uint64_t> &offs) {
     if (!buf || len < 8) return fail("tiff: input too short");
     TiffReader t{buf, len, true};
@@ -280,7 +284,8 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
     const uint64_t ne = t.big ? t.u64(ifd) : t.u16(ifd);
     uint32_t w = 0, h = 0, spp = 1, bps = 8, comp = 1, planar = 1, rps = 0xFFFFFFFFu, fmt = 1, pred = 1;
     uint32_t photo = 0xFFFFFFFFu;  // absent: inferred from SamplesPerPixel
-    size_t e_off = 0, e_cnt = 0;
+    uint32_t fill = 1;             // FillOrder: MSB-first when absent
+    size_t e_off = 0, e_cnt = 0, e_cmap = 0;
     uint32_t n_off = 0, tw = 0, th = 0;
     // what the file states about its pixels (the JP2 / JPX header carries it):
     // a malformed one of these tags is an absent one
@@ -298,6 +303,8 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
         case 258: bps = (uint32_t)t.val(e, 0); break;
         case 259: comp = (uint32_t)t.val(e, 0); break;
         case 262: photo = (uint32_t)t.val(e, 0); break;
+        case 266: fill = (uint32_t)t.val(e, 0); break;
+        case 320: e_cmap = e; break;  // ColorMap
         case 273: e_off = e; n_off = (uint32_t)std::min<uint64_t>(t.count(e), 0xFFFFFFFFu); break;
         case 277: spp = (uint32_t)t.val(e, 0); break;
         case 278: rps = (uint32_t)std::min<uint64_t>(t.val(e, 0), 0xFFFFFFFFu); break;
@@ -349,17 +356,40 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
     if (pred != 1 && pred != 2) return fail("tiff: predictor " + std::to_string(pred) + " is not supported");
     if (pred == 2 && comp == 1) return fail("tiff: predictor 2 without compression is not supported");
     if (comp != 1 && !e_cnt) return fail("tiff: compressed strips need StripByteCounts");
-    if (bps != 8 && bps != 16) return fail("tiff: " + std::to_string(bps) + " bits/sample is not supported");
+    if (bps != 1 && bps != 2 && bps != 4 && bps != 8 && bps != 16)
+        return fail("tiff: " + std::to_string(bps) + " bits/sample is not supported");
+    if (bps < 8 && spp != 1)
+        return fail("tiff: " + std::to_string(bps) + " bits/sample with " + std::to_string(spp) +
+                    " samples/pixel is not supported (packed samples: one per pixel only)");
+    if (bps < 8 && pred == 2)
+        return fail("tiff: predictor 2 with " + std::to_string(bps) + " bits/sample is not supported");
+    if (bps < 8 && fill != 1 && fill != 2) return fail("tiff: FillOrder " + std::to_string(fill) + " is not supported");
     if (fmt != 1) return fail("tiff: only unsigned integer samples are supported");
     if (spp < 1 || spp > 4) return fail("tiff: " + std::to_string(spp) + " samples/pixel is not supported");
     if (planar != 1 && planar != 2) return fail("tiff: bad PlanarConfiguration");
     // PhotometricInterpretation: BlackIsZero gray (+ alpha) or RGB (+ alpha);
     // the colour transform assumes RGB in components 0..2
     if (photo == 0xFFFFFFFFu) photo = spp >= 3 ? 2 : 1;
-    if (photo == 0) return fail("tiff: PhotometricInterpretation 0 (WhiteIsZero) is not supported");
-    if (photo != 1 && photo != 2)
+    // WhiteIsZero: the 1-, 2- and 4-bit forms only (bilevel scans; expanded and
+    // inverted by k_expand)
+    if (photo == 0 && bps >= 8) return fail("tiff: PhotometricInterpretation 0 (WhiteIsZero) is not supported");
+    const uint8_t *cmap = nullptr;
+    if (photo == 3) {  // palette colour: indices of 1, 2, 4 or 8 bits and a whole ColorMap
+        if (spp != 1) return fail("tiff: PhotometricInterpretation 3 (palette) needs 1 sample/pixel");
+        if (bps > 8)
+            return fail("tiff: PhotometricInterpretation 3 (palette) with " + std::to_string(bps) +
+                        "-bit indices is not supported");
+        if (!e_cmap) return fail("tiff: PhotometricInterpretation 3 (palette) without a ColorMap is not supported");
+        size_t at;
+        if (t.u16(e_cmap + 2) != 3 || t.count(e_cmap) != (3ull << bps) || !t.data_at(e_cmap, 2, 3ull << bps, at))
+            return fail("tiff: PhotometricInterpretation 3 (palette): the ColorMap must be 3 * 2^" +
+                        std::to_string(bps) + " SHORTs inside the file");
+        cmap = buf + at;
+    } else if (photo != 0 && photo != 1 && photo != 2) {
         return fail("tiff: PhotometricInterpretation " + std::to_string(photo) +
-                    " is not supported (BlackIsZero gray or RGB only)");
+                    " is not supported (gray, RGB or palette only)");
+    }
+    if (photo == 0 && spp != 1) return fail("tiff: WhiteIsZero with more than 1 sample/pixel is not supported");
     if (photo == 2 && spp < 3) return fail("tiff: RGB needs 3 or 4 samples/pixel");
     if (photo == 1 && spp > 2) return fail("tiff: BlackIsZero with more than 2 samples/pixel is not supported");
     if (rps == 0 && !tiled) rps = h;  // RowsPerStrip 0 is invalid; libtiff reads it as one strip
@@ -371,7 +401,7 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
     if (n_off < need) return fail(tiled ? "tiff: too few tiles" : "tiff: too few strips");
     const bool packed = comp != 1 || tiled;
     offs.resize(packed ? 2 * (size_t)need : need);
-    size_t row = (size_t)w * (planar == 2 ? 1 : spp) * (bps / 8);
+    const size_t row = packed_row_bytes(w, planar == 2 ? 1 : spp, bps);
     for (uint32_t s = 0; s < need; s++) {
         offs[s] = t.val(e_off, s);
         uint32_t y0 = (s % per_plane) * rps;
@@ -379,7 +409,7 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
         if (packed) {
             const uint64_t nb = t.val(e_cnt, s);
             if (offs[s] > len || nb > len - offs[s]) return fail("tiff: strip " + std::to_string(s) + " out of range");
-            const uint64_t unit = (uint64_t)tw * (planar == 2 ? 1 : spp) * (bps / 8) * th;
+            const uint64_t unit = packed_row_bytes(tw, planar == 2 ? 1 : spp, bps) * th;
             if (tiled && comp == 1 && nb < unit) return fail("tiff: tile byte count too small");
             offs[need + s] = nb;
             continue;
@@ -413,6 +443,10 @@ int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<u
     lay->yres_den = res ? yr[1] : 0;
     lay->icc = icc;
     lay->icc_bytes = icc_bytes;
+    lay->photometric = photo == 3 ? JP2HIP_PHOTO_PALETTE : (photo == 0 ? JP2HIP_PHOTO_WHITE_IS_ZERO : JP2HIP_PHOTO_DEFAULT);
+    lay->fill_order = bps < 8 ? (int32_t)fill : 0;
+    lay->colormap = cmap;
+    lay->colormap_entries = cmap ? (3ull << bps) : 0;
     return 0;
 }
 
@@ -447,20 +481,90 @@ int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h) {
     return (int64_t)std::floor(rc.rate_bpp * (double)w * (double)h / 8.0);
 }
 
+// Sources whose samples are expanded to 8 bits in HBM before ingest
+// (expand.hip): 1-, 2- and 4-bit grey and palette colour.
+bool needs_expand(const jp2hip_layout &lay) { return lay.bits < 8 || lay.photometric == JP2HIP_PHOTO_PALETTE; }
+
+// What the code-stream carries for this source (jp2hip_encoded_format).
+void encoded_format(const jp2hip_layout &lay, int &nc, int &bits) {
+    nc = lay.photometric == JP2HIP_PHOTO_PALETTE ? 3 : lay.components;
+    bits = needs_expand(lay) ? 8 : lay.bits;
+}
+
+// The pixel format of a layout, the parser's or a caller's: the depths,
+// component counts and photometric forms the encoder has a path for.
+bool check_pixel_format(const jp2hip_layout *lay, std::string &err) {
+    const int b = lay->bits;
+    if (b != 1 && b != 2 && b != 4 && b != 8 && b != 16) {
+        err = "layout: " + std::to_string(b) + " bits/sample is not supported";
+        return false;
+    }
+    if (lay->components < 1 || lay->components > 4 || (lay->planar != 1 && lay->planar != 2)) {
+        err = "layout: bad geometry or strip table";
+        return false;
+    }
+    if (lay->photometric != JP2HIP_PHOTO_DEFAULT && lay->photometric != JP2HIP_PHOTO_WHITE_IS_ZERO &&
+        lay->photometric != JP2HIP_PHOTO_PALETTE) {
+        err = "layout: unknown photometric " + std::to_string(lay->photometric);
+        return false;
+    }
+    if (b < 8 && lay->components != 1) {
+        err = "layout: samples below 8 bits need 1 component";
+        return false;
+    }
+    if (b < 8 && (lay->fill_order < 0 || lay->fill_order > 2)) {
+        err = "layout: fill_order must be 0, 1 or 2";
+        return false;
+    }
+    if (b < 8 && lay->predictor == 2) {
+        err = "layout: predictor 2 with samples below 8 bits is not supported";
+        return false;
+    }
+    if (lay->photometric == JP2HIP_PHOTO_WHITE_IS_ZERO && (b >= 8 || lay->components != 1)) {
+        err = "layout: photometric WhiteIsZero is supported for 1 component of 1, 2 or 4 bits only";
+        return false;
+    }
+    if (lay->photometric == JP2HIP_PHOTO_PALETTE &&
+        (b > 8 || lay->components != 1 || !lay->colormap || lay->colormap_entries != (3ull << b))) {
+        err = "layout: photometric palette needs 1 component of 1, 2, 4 or 8 bits and a colormap of 3 * 2^bits entries";
+        return false;
+    }
+    if (needs_expand(*lay) && lay->tile_width > 0 && lay->tile_width % 16) {
+        err = "layout: tiles of packed samples or palette indices need a tile_width in multiples of 16";
+        return false;
+    }
+    return true;
+}
+
+// The colour table of a palette layout as k_expand reads it: entry i is
+// R | G << 8 | B << 16.  ColorMap values are 16-bit (a component is the high
+// byte) unless no entry exceeds 255: such maps, from old writers, hold 8-bit
+// values and are taken as they are (libtiff's checkcmap).
+void palette_lut(const jp2hip_layout &lay, uint32_t *lut) {
+    const int n = 1 << lay.bits;
+    auto entry = [&](int i) -> uint32_t {
+        const uint8_t *p = lay.colormap + 2 * (size_t)i;
+        return lay.big_endian ? ((uint32_t)p[0] << 8) | p[1] : p[0] | ((uint32_t)p[1] << 8);
+    };
+    bool wide = false;
+    for (int i = 0; i < 3 * n; i++) wide = wide || entry(i) > 255;
+    const int sh = wide ? 8 : 0;
+    for (int i = 0; i < n; i++)
+        lut[i] = (entry(i) >> sh) | ((entry(n + i) >> sh) << 8) | ((entry(2 * n + i) >> sh) << 16);
+}
+
 // A caller-supplied layout (jp2hip_encode_device*) is checked against the
 // source buffer before any kernel reads it: the strips that rows [row0, row1)
 // touch must lie inside src_len (uncompressed), tiles must hold a whole tile
 // (uncompressed tiled), and compressed strips are checked in
 // unpack_if_compressed.
 bool validate_layout(const jp2hip_layout *lay, size_t src_len, int row0, int row1, std::string &err) {
-    if (lay->width <= 0 || lay->height <= 0 || lay->components < 1 || lay->components > 4 ||
-        (lay->bits != 8 && lay->bits != 16) || (lay->planar != 1 && lay->planar != 2) || lay->rows_per_strip <= 0 ||
-        lay->nstrips <= 0 || !lay->strip_offsets) {
+    if (lay->width <= 0 || lay->height <= 0 || lay->rows_per_strip <= 0 || lay->nstrips <= 0 || !lay->strip_offsets) {
         err = "layout: bad geometry or strip table";
         return false;
     }
+    if (!check_pixel_format(lay, err)) return false;
     const uint64_t spp_row = lay->planar == 2 ? 1 : (uint64_t)lay->components;
-    const uint64_t px = spp_row * (uint64_t)(lay->bits / 8);
     const int planes = lay->planar == 2 ? lay->components : 1;
     if (lay->tile_width > 0 || lay->tile_height > 0) {
         if (lay->tile_width <= 0 || lay->tile_height <= 0 || !lay->strip_bytes) {
@@ -470,7 +574,7 @@ bool validate_layout(const jp2hip_layout *lay, size_t src_len, int row0, int row
         const int64_t across = (lay->width + lay->tile_width - 1) / lay->tile_width;
         const int64_t need = across * ((lay->height + lay->tile_height - 1) / lay->tile_height) * planes;
         if (need > lay->nstrips) { err = "layout: too few tiles"; return false; }
-        const uint64_t unit = (uint64_t)lay->tile_width * lay->tile_height * px;
+        const uint64_t unit = packed_row_bytes(lay->tile_width, spp_row, lay->bits) * lay->tile_height;
         for (int64_t i = 0; i < need; i++) {
             const uint64_t o = lay->strip_offsets[i], n = lay->strip_bytes[i];
             if (o > src_len || n > src_len - o || (lay->compression <= 1 && n < unit)) {
@@ -483,7 +587,7 @@ bool validate_layout(const jp2hip_layout *lay, size_t src_len, int row0, int row
     if (lay->compression > 1) return true;  // checked with the strip byte counts in unpack_if_compressed
     const int64_t per_plane = (lay->height + (int64_t)lay->rows_per_strip - 1) / lay->rows_per_strip;
     if (per_plane * planes > lay->nstrips) { err = "layout: too few strips"; return false; }
-    const uint64_t row_bytes = (uint64_t)lay->width * px;
+    const uint64_t row_bytes = packed_row_bytes(lay->width, spp_row, lay->bits);
     const int64_t s0 = std::max(0, row0) / lay->rows_per_strip;
     const int64_t s1 = std::min<int64_t>(per_plane, ((int64_t)std::min(row1, lay->height) + lay->rows_per_strip - 1) /
                                                         lay->rows_per_strip);
@@ -537,11 +641,11 @@ bool unpack_band(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2h
     if (lay->compression <= 1 && lay->tile_width <= 0) return true;
     const bool tiled = lay->tile_width > 0;
     if (lay->width <= 0 || lay->height <= 0 || !lay->strip_offsets || !lay->strip_bytes ||
-        (tiled && lay->tile_height <= 0) || (!tiled && lay->rows_per_strip <= 0) || (lay->planar != 1 && lay->planar != 2) ||
-        lay->components < 1 || (lay->bits != 8 && lay->bits != 16)) {
+        (tiled && lay->tile_height <= 0) || (!tiled && lay->rows_per_strip <= 0)) {
         err = "layout: compressed strips / tiles need a geometry, strip_offsets and strip_bytes";
         return false;
     }
+    if (!check_pixel_format(lay, err)) return false;
     const int uh = tiled ? lay->tile_height : lay->rows_per_strip;  // rows per unit
     const int planes = lay->planar == 2 ? lay->components : 1;
     const int64_t across = tiled ? (lay->width + lay->tile_width - 1) / lay->tile_width : 1;
@@ -558,8 +662,8 @@ bool unpack_band(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2h
         return false;
     }
     const int R0 = (int)(u0 * uh), R1 = (int)std::min<int64_t>(lay->height, u1 * uh);
-    const uint64_t px = (uint64_t)(lay->planar == 2 ? 1 : lay->components) * (uint64_t)(lay->bits / 8);
-    const uint64_t unit = tiled ? (uint64_t)lay->tile_width * lay->tile_height * px : 0;
+    const uint64_t spp_row = lay->planar == 2 ? 1 : (uint64_t)lay->components;
+    const uint64_t unit = tiled ? packed_row_bytes(lay->tile_width, spp_row, lay->bits) * lay->tile_height : 0;
     std::vector<uint64_t> voff, vcnt;
     for (int p = 0; p < planes; p++)
         for (int64_t u = u0; u < u1; u++)
@@ -583,7 +687,7 @@ bool unpack_band(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2h
     const void *d2 = nullptr;
     if (!ctx->gpu.unpack_strips(d_src, v, vu, vuoffs, &d2, err)) return false;
     // the full-image view: unit row u of plane p at its decoded place
-    const uint64_t row_bytes = (uint64_t)lay->width * px;
+    const uint64_t row_bytes = packed_row_bytes(lay->width, spp_row, lay->bits);
     ulay = vu;
     ulay.height = lay->height;
     ulay.rows_per_strip = uh;
@@ -595,6 +699,103 @@ bool unpack_band(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2h
                                                    : vuoffs[(size_t)(p * (u1 - u0) + (u - u0))];
     ulay.strip_offsets = uoffs.data();
     d_src = d2;
+    lay = &ulay;
+    return true;
+}
+
+// S1b: a source of 1-, 2-, 4-bit samples or palette indices (needs_expand)
+// becomes 8-bit samples in HBM.  Only the units (strips or tiles) that image
+// rows [row0, row1) touch are read -- they alone must lie inside d_src, so a
+// tile-split rank passes its band -- decoded first when they are compressed
+// (as tiles they stay tiles: the expansion untiles), then expanded into a
+// copy sized by those rows.  Afterwards (d_src, lay) describe the whole
+// image as uncompressed 8-bit strips, grey or chunky RGB, of which the
+// entries outside the band are never read (as after unpack_band).
+bool expand_source(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2hip_layout *&lay, int row0, int row1,
+                   jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err) {
+    const bool tiled = lay->tile_width > 0 || lay->tile_height > 0, decode = lay->compression > 1;
+    if (lay->width <= 0 || lay->height <= 0 || !lay->strip_offsets || lay->nstrips <= 0 ||
+        (tiled && (lay->tile_width <= 0 || lay->tile_height <= 0)) || (!tiled && lay->rows_per_strip <= 0) ||
+        ((tiled || decode) && !lay->strip_bytes)) {
+        err = "layout: bad geometry or strip table (compressed strips and tiles need strip_bytes)";
+        return false;
+    }
+    if (!check_pixel_format(lay, err)) return false;
+    if (decode && lay->compression != 5 && lay->compression != 8 && lay->compression != 32946 &&
+        lay->compression != 32773) {
+        err = "layout: compression " + std::to_string(lay->compression) + " is not supported";
+        return false;
+    }
+    const int uh = tiled ? lay->tile_height : lay->rows_per_strip;  // rows per unit
+    const int64_t across = tiled ? (lay->width + (int64_t)lay->tile_width - 1) / lay->tile_width : 1;
+    const int64_t urows = (lay->height + (int64_t)uh - 1) / uh;
+    if (across * urows > lay->nstrips) {
+        err = tiled ? "layout: too few tiles" : "layout: too few strips";
+        return false;
+    }
+    const int64_t u0 = std::max(0, row0) / uh;
+    const int64_t u1 = std::min<int64_t>(urows, ((int64_t)std::min(row1, lay->height) + uh - 1) / uh);
+    if (u1 <= u0) {
+        err = "layout: empty band";
+        return false;
+    }
+    const int R0 = (int)(u0 * uh), R1 = (int)std::min<int64_t>(lay->height, u1 * uh);
+    const uint64_t unit_row = packed_row_bytes(tiled ? lay->tile_width : lay->width, 1, lay->bits);
+    std::vector<uint64_t> voff, vcnt;
+    for (int64_t u = u0; u < u1; u++)
+        for (int64_t x = 0; x < across; x++) {
+            const size_t i = (size_t)(u * across + x);
+            const uint64_t o = lay->strip_offsets[i];
+            // what the expansion reads of an uncompressed unit; a compressed one is read whole
+            const uint64_t rows = tiled ? (uint64_t)uh : (uint64_t)std::min<int64_t>(uh, lay->height - u * uh);
+            const uint64_t n = lay->strip_bytes ? lay->strip_bytes[i] : rows * unit_row;
+            if (o > src_len || n > src_len - o || (!decode && n < rows * unit_row)) {
+                err = "layout: strip / tile " + std::to_string(i) + " lies outside the source buffer or is short";
+                return false;
+            }
+            voff.push_back(o);
+            vcnt.push_back(n);
+        }
+    jp2hip_layout v = *lay;
+    v.height = R1 - R0;
+    v.nstrips = (int32_t)voff.size();
+    v.strip_offsets = voff.data();
+    v.strip_bytes = vcnt.data();
+    jp2hip_layout vu;
+    std::vector<uint64_t> vuoffs;
+    const jp2hip_layout *cur = &v;
+    const void *d = d_src;
+    if (decode) {
+        if (!ctx->gpu.unpack_strips(d_src, v, vu, vuoffs, &d, err, false)) return false;
+        cur = &vu;
+    }
+    // the colour table: per encode, never with the cached plan (two files of
+    // one geometry have their own maps)
+    uint32_t lut[256];
+    const bool palette = lay->photometric == JP2HIP_PHOTO_PALETTE;
+    if (palette) palette_lut(*lay, lut);
+    const void *d8 = nullptr;
+    if (!ctx->gpu.expand_samples(d, *cur, R1 - R0, palette ? lut : nullptr, ctx->cfg.profile != 0, &d8, err)) return false;
+    int nc, bits;
+    encoded_format(*lay, nc, bits);
+    ulay = *lay;
+    ulay.components = nc;
+    ulay.bits = bits;
+    ulay.planar = 1;
+    ulay.rows_per_strip = uh;
+    ulay.nstrips = (int32_t)urows;
+    ulay.compression = 1;
+    ulay.predictor = 1;
+    ulay.strip_bytes = nullptr;
+    ulay.tile_width = ulay.tile_height = 0;
+    ulay.photometric = JP2HIP_PHOTO_DEFAULT;
+    ulay.fill_order = 0;
+    ulay.colormap = nullptr;
+    ulay.colormap_entries = 0;
+    uoffs.assign((size_t)urows, 0);
+    for (int64_t u = u0; u < u1; u++) uoffs[(size_t)u] = (uint64_t)(u - u0) * uh * lay->width * nc;
+    ulay.strip_offsets = uoffs.data();
+    d_src = d8;
     lay = &ulay;
     return true;
 }
@@ -673,7 +874,9 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     jp2hip_layout ulay;
     std::vector<uint64_t> uoffs;
     if (!validate_layout(lay, src_len, 0, lay->height, err)) return fail(err);
-    if (!unpack_if_compressed(ctx, d_src, src_len, lay, ulay, uoffs, err)) return fail(err);
+    if (needs_expand(*lay) ? !expand_source(ctx, d_src, src_len, lay, 0, lay->height, ulay, uoffs, err)
+                           : !unpack_if_compressed(ctx, d_src, src_len, lay, ulay, uoffs, err))
+        return fail(err);
     PlanCache &pc = ctx->pc;
     if (!pc.valid || pc.w != lay->width || pc.h != lay->height || pc.nc != lay->components || pc.bits != lay->bits ||
         std::memcmp(&pc.rc, &rc, sizeof rc) != 0) {
@@ -815,7 +1018,10 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     EncodeEnd end{ctx};
     Plan full;
     std::string err;
-    if (!build_plan(full, rc, lay->width, lay->height, lay->components, lay->bits, err)) return fail(err);
+    if (!check_pixel_format(lay, err)) return fail(err);
+    int enc_nc, enc_bits;  // the plan sees what the code-stream carries
+    encoded_format(*lay, enc_nc, enc_bits);
+    if (!build_plan(full, rc, lay->width, lay->height, enc_nc, enc_bits, err)) return fail(err);
     int tr0, tr1;
     split_tile_rows(full.nty, rc.tile_h, full.h, rc.flush_period, rank, world, tr0, tr1);
     Plan sub;
@@ -827,8 +1033,10 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     jp2hip_layout ulay;
     std::vector<uint64_t> uoffs;
     const bool packed = lay->compression > 1 || lay->tile_width > 0;
-    bool ok = !have || (packed ? unpack_band(ctx, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err)
-                               : validate_layout(lay, src_len, sub.row0, sub.row0 + sub.band_h, err));
+    bool ok = !have ||
+              (needs_expand(*lay) ? expand_source(ctx, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err)
+               : packed           ? unpack_band(ctx, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err)
+                                  : validate_layout(lay, src_len, sub.row0, sub.row0 + sub.band_h, err));
     const bool prof = ctx->cfg.profile != 0;
     StageTimes st;
     std::vector<uint64_t> keys;
@@ -1104,7 +1312,7 @@ bool band_units(const jp2hip_layout &lay, size_t flen, int row0, int row1, std::
         err = tiled ? "layout: too few tiles" : "layout: too few strips";
         return false;
     }
-    const uint64_t row_bytes = (uint64_t)lay.width * (uint64_t)(lay.planar == 2 ? 1 : lay.components) * (lay.bits / 8);
+    const uint64_t row_bytes = packed_row_bytes(lay.width, lay.planar == 2 ? 1 : lay.components, lay.bits);
     const int64_t u0 = row0 / uh, u1 = std::min<int64_t>(urows, (row1 + (int64_t)uh - 1) / uh);
     for (int p = 0; p < planes; p++)
         for (int64_t u = u0; u < u1; u++)
@@ -1463,6 +1671,15 @@ int jp2hip_tiff_layout(const uint8_t *tiff, size_t len, jp2hip_layout *layout, u
     return 0;
 }
 
+int jp2hip_encoded_format(const jp2hip_layout *layout, int32_t *components, int32_t *bits) {
+    if (!layout || !components || !bits) return fail("null argument");
+    int nc, b;
+    encoded_format(*layout, nc, b);
+    *components = nc;
+    *bits = b;
+    return 0;
+}
+
 int64_t jp2hip_file_header(const jp2hip_layout *layout, int32_t format, uint64_t codestream_bytes, uint8_t *dst,
                            size_t cap) {
     if (!layout) return fail("null layout");
@@ -1474,8 +1691,7 @@ int64_t jp2hip_file_header(const jp2hip_layout *layout, int32_t format, uint64_t
     hdr.rc.format = format;
     hdr.w = layout->width;
     hdr.h = layout->height;
-    hdr.nc = layout->components;
-    hdr.bits = layout->bits;
+    encoded_format(*layout, hdr.nc, hdr.bits);
     const jp2hip::SourceMeta meta = jp2hip::source_meta(*layout);
     const size_t n = jp2hip::file_header_bytes(hdr, meta);
     if (n && dst && cap >= n) jp2hip::write_file_header(hdr, meta, codestream_bytes, dst);

@@ -2,7 +2,7 @@
 // memory accounting (the buffers themselves are listed in gpu_encoder.h),
 // the pinned staging ring of host -> device copies, host waits, debug dumps
 // and the stage times read from the events.  The members that enqueue a
-// stage live next to its kernels (unpack.hip, front.hip, pcrd.hip,
+// stage live next to its kernels (unpack.hip, expand.hip, front.hip, pcrd.hip,
 // t2_device.hip).
 #include <algorithm>
 #include <atomic>
@@ -217,6 +217,10 @@ bool GpuEncoder::collect_profile(StageTimes &st, std::string &err) {
     if (!profiled || !h_tot) return true;
     float t;
     HIPCHECK(hipEventElapsedTime(&t, ev[kEvFrontBegin], ev[kEvDwtBegin])); st.ingest = t;
+    if (expand_timed) {
+        HIPCHECK(hipEventElapsedTime(&t, ev[kEvExpandBegin], ev[kEvExpandEnd]));
+        st.ingest += t;
+    }
     HIPCHECK(hipEventElapsedTime(&t, ev[kEvDwtBegin], ev[kEvDwtEnd])); st.dwt = t;
     HIPCHECK(hipEventElapsedTime(&t, ev[kEvDwtEnd], ev[kEvQuantEnd])); st.quant = t;
     HIPCHECK(hipEventElapsedTime(&t, ev[kEvCmBegin], ev[kEvCmEnd])); st.t1_cm = t;

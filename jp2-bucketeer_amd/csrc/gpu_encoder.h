@@ -46,7 +46,9 @@ struct FrontJob;  // front.hip
     X(grptab) X(gtot)                                                                                         \
     /* device tier-2 (t2_device.hip) */                                                                       \
     X(hdist) X(rstate) X(t2ticket) X(t2prec) X(t2tp) X(t2tt) X(t2lblock) X(t2incl) X(t2pklen) X(t2pkoff)      \
-    X(t2tplen) X(t2tphdr) X(t2tpoff) X(t2blkdst) X(t2out) X(t2sum)
+    X(t2tplen) X(t2tphdr) X(t2tpoff) X(t2blkdst) X(t2out) X(t2sum)                                            \
+    /* S1b sample expansion (expand.hip): the 8-bit copy, its unit offsets and the colour table */           \
+    X(expanded) X(exoff) X(exlut)
 
 // Owns all device memory of a context; buffers only grow while the context
 // stays within its soft limit, so repeated encodes of the same geometry never
@@ -78,6 +80,7 @@ class GpuEncoder {
     // keep the size of the largest image since the last trim)
     void begin_encode() {
         for (DevBuf *b : bufs()) b->want = 0;
+        expand_timed = false;
     }
     size_t need_bytes() {
         size_t n = 0;
@@ -97,9 +100,17 @@ class GpuEncoder {
     bool upload_source(const void *host, size_t len, std::string &err);
     const void *source() const { return src.ptr; }
     // LZW / PackBits strips (+ Predictor 2) -> an uncompressed staging copy
-    // in HBM; `out` describes it (offsets in out_offs)
+    // in HBM; `out` describes it (offsets in out_offs).  untile = false
+    // (sources that expand_samples reads next, which untiles itself): decoded
+    // tiles stay tiles, one per entry of out_offs
     bool unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2hip_layout &out,
-                       std::vector<uint64_t> &out_offs, const void **d_out, std::string &err);
+                       std::vector<uint64_t> &out_offs, const void **d_out, std::string &err, bool untile = true);
+
+    // S1b (expand.hip): `rows` rows of uncompressed 1-, 2-, 4-bit samples or
+    // palette indices (lut: 2^bits packed colours, else nullptr) -> 8-bit
+    // samples in the `expanded` buffer, one row-major strip; enqueued only
+    bool expand_samples(const void *d_src, const jp2hip_layout &lay, int rows, const uint32_t *lut, bool profile,
+                        const void **d_out, std::string &err);
 
     // Sums a slope-prediction histogram over the ranks of a tile-split
     // encode, in place; false = exchange failed (or another rank failed).
@@ -227,6 +238,8 @@ class GpuEncoder {
         kEvSelectEnd,
         kEvT2Begin,      // .. kEvT2End = t2 (t2_size) or d2h (t2_emit)
         kEvT2End,
+        kEvExpandBegin,  // expand_samples: .. kEvExpandEnd = ingest (k_expand; before kEvFrontBegin)
+        kEvExpandEnd,
         kNumEvents
     };
     int device = 0;
@@ -245,6 +258,7 @@ class GpuEncoder {
     T2Summary *h_sum = nullptr;
     int64_t *h_tot = nullptr;  // pinned [8]: t1 total, -, k_t1_mq span[2], unpack error, segment tail[2]
     bool profiled = false;
+    bool expand_timed = false;  // this encode recorded kEvExpandBegin / End
     int nseg = 0;  // hull segments at most: the bound sum(3 Mb - 2)
     std::vector<int64_t> h_hist;
     std::vector<uint64_t> strips_host;  // strip offsets last uploaded to `strips`

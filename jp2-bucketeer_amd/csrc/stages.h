@@ -1,7 +1,7 @@
 // stages.h -- what the stage files export to GpuEncoder's members: argument
-// structs and launchers of the strip decoders (unpack.hip, lzw.hip), the fused
-// ingest + DWT (dwt.hip) and tier-1 (t1.hip).  Argument structs that only
-// one file uses stay in that file.
+// structs and launchers of the strip decoders (unpack.hip, lzw.hip), the
+// sample expansion (expand.hip), the fused ingest + DWT (dwt.hip) and tier-1
+// (t1.hip).  Argument structs that only one file uses stay in that file.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +21,25 @@ namespace jp2hip {
 uint64_t lzw_slices(const uint64_t *strip_bytes, int nstrips, std::vector<uint64_t> &slice);
 size_t lzw_scratch_bytes(int nstrips, uint64_t segs);
 bool launch_lzw(const UnpackArgs &u, uint64_t segs, void *scratch, hipStream_t st);
+
+// S1b sample expansion (expand.hip): packed 1-, 2-, 4-bit samples or palette
+// indices (1, 2, 4, 8 bits), one sample per pixel, in strips or tiles ->
+// row-major 8-bit samples, grey or chunky RGB.  Unit u (strip, or tile in
+// row-major tile order) starts at src + off[u]; its rows are row_bytes apart.
+struct ExpandArgs {
+    const uint8_t *src;
+    const uint64_t *off;   // [units] device table
+    int w, rows;           // pixels per output row, output rows
+    int unit_w, unit_h;    // pixels per unit row (w for strips), rows per unit
+    int across;            // units side by side (1 for strips)
+    uint32_t row_bytes;    // ceil(unit_w * bits / 8)
+    int lsb_first;         // FillOrder 2: the bits of every source byte reversed first
+    uint32_t invert;       // WhiteIsZero: 0xFFFFFFFF, XORed onto every output dword (else 0)
+    const uint32_t *lut;   // palette: [2^bits] dwords R | G << 8 | B << 16
+    uint8_t *dst;          // rows * w bytes (grey), rows * w * 3 (palette)
+};
+// false: bits is not 1, 2, 4 (or 8 with a palette), or a launch error
+bool launch_expand(const ExpandArgs &a, int bits, bool palette, hipStream_t st);
 
 // the SDMA engines chosen per GPU and their probed rates (t2_device.hip)
 std::string dma_engine_report();

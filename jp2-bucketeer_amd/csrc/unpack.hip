@@ -96,18 +96,23 @@ __global__ void __launch_bounds__(256) k_untile(const uint8_t *base, const uint6
 }
 
 bool GpuEncoder::unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2hip_layout &out,
-                               std::vector<uint64_t> &out_offs, const void **d_out, std::string &err) {
+                               std::vector<uint64_t> &out_offs, const void **d_out, std::string &err,
+                               bool untile) {
     HIPCHECK(hipSetDevice(device));
     const int ns = lay.nstrips;  // strips, or tiles
     const bool tiled = lay.tile_width > 0;
     const int spp_row = lay.planar == 2 ? 1 : lay.components;
-    const int px_bytes = spp_row * (lay.bits / 8);
+    const int px_bytes = spp_row * (lay.bits / 8);  // (0 below 8 bits: such tiles are not untiled here)
     const int unit_w = tiled ? lay.tile_width : lay.width, unit_h = tiled ? lay.tile_height : lay.rows_per_strip;
     const int planes = lay.planar == 2 ? lay.components : 1;
     const int across = tiled ? (lay.width + lay.tile_width - 1) / lay.tile_width : 1;
     const int per_plane = tiled ? across * ((lay.height + lay.tile_height - 1) / lay.tile_height)
                                 : (lay.height + lay.rows_per_strip - 1) / lay.rows_per_strip;
-    const uint64_t row_bytes = (uint64_t)unit_w * px_bytes;
+    const uint64_t row_bytes = ((uint64_t)unit_w * spp_row * lay.bits + 7) / 8;  // rows start on byte boundaries
+    if (lay.bits < 8 && ((tiled && untile) || lay.predictor == 2)) {
+        err = "layout: samples below 8 bits are neither untiled nor un-differenced here";
+        return false;
+    }
     const uint64_t stride = ((uint64_t)unit_h * row_bytes + 255) & ~255ull;
     const bool decode = lay.compression > 1;
     if (!ensure<uint64_t>(soff, (size_t)ns * 2, err) || !ensure<int>(this->err, 4, err)) return false;
@@ -168,8 +173,8 @@ bool GpuEncoder::unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2h
     }
     const void *res = decode ? stage.ptr : d_src;
     out = lay;
-    out_offs.resize(tiled ? planes : ns);
-    if (tiled) {  // tiles -> one row-major strip per plane
+    out_offs.resize(tiled && untile ? planes : ns);
+    if (tiled && untile) {  // tiles -> one row-major strip per plane
         const uint64_t plane_bytes = (uint64_t)lay.width * lay.height * px_bytes;
         if (!ensure<uint8_t>(untiled, plane_bytes * planes, err)) return false;
         hipLaunchKernelGGL(k_untile, dim3((lay.width + 255) / 256, lay.height, planes), dim3(256), 0, stream,

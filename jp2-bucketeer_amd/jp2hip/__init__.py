@@ -4,11 +4,12 @@
 ``jp2hip._lib`` binds the C ABI of libjp2hip (include/jp2hip.h).
 """
 from ._lib import (FORMAT_J2K, FORMAT_JP2, FORMAT_JPX, LOSSLESS, LOSSY, Encoder, Jp2hipError, Output,
-                   device_count, device_ordinals, file_header, probe, recipe, tiff_layout, version)
+                   device_count, device_ordinals, encoded_format, file_header, probe, recipe, tiff_layout,
+                   version)
 from .converters import (Conversion, Converter, ConverterFactory, GpuConverter,
                          KakaduConverter, KakaduNotFoundError, OpenJPEGConverter)
 
 __all__ = ["Conversion", "Converter", "ConverterFactory", "GpuConverter", "KakaduConverter",
            "KakaduNotFoundError", "OpenJPEGConverter", "Encoder", "Jp2hipError", "LOSSY",
            "LOSSLESS", "FORMAT_J2K", "FORMAT_JP2", "FORMAT_JPX", "Output", "device_count", "device_ordinals",
-           "file_header", "probe", "recipe", "tiff_layout", "version"]
+           "encoded_format", "file_header", "probe", "recipe", "tiff_layout", "version"]

@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("JP2HIP_LIBRARY") or os.path.join(HERE, "libjp2hip.so"
 LOSSY = 0      # Conversion.LOSSY    (Conversion.java:9)
 LOSSLESS = 1   # Conversion.LOSSLESS (Conversion.java:9)
 FORMAT_J2K, FORMAT_JP2, FORMAT_JPX = 0, 1, 2
+# Layout.photometric (JP2HIP_PHOTO_*)
+PHOTO_DEFAULT, PHOTO_WHITE_IS_ZERO, PHOTO_PALETTE = 0, 1, 2
 
 
 class Jp2hipError(OSError):
@@ -52,9 +54,14 @@ class Layout(Structure):
                 ("extra_samples", c_int32), ("res_unit", c_int32),
                 ("xres_num", c_uint32), ("xres_den", c_uint32),
                 ("yres_num", c_uint32), ("yres_den", c_uint32),
-                ("icc", POINTER(c_uint8)), ("icc_bytes", c_uint64)]
+                ("icc", POINTER(c_uint8)), ("icc_bytes", c_uint64),
+                # the pixel format (zero: BlackIsZero grey / RGB samples as they
+                # are): bits may be 1, 2, 4; palette indices come with a colormap
+                ("photometric", c_int32), ("fill_order", c_int32),
+                ("colormap", POINTER(c_uint8)), ("colormap_entries", c_uint64)]
 
     METADATA = ("extra_samples", "res_unit", "xres_num", "xres_den", "yres_num", "yres_den")
+    PIXEL_FORMAT = ("photometric", "fill_order", "colormap", "colormap_entries")
 
     def icc_profile(self) -> bytes:
         """The ICC profile bytes the layout points at (b"" when it has none)."""
@@ -71,6 +78,27 @@ class Layout(Structure):
         for name in Layout.METADATA:
             setattr(self, name, getattr(src, name))
         self.set_icc_profile(src.icc_profile())
+
+    def colormap_bytes(self) -> bytes:
+        """The ColorMap data the layout points at: colormap_entries 16-bit
+        values in the file's byte order (b"" when it has none)."""
+        n = 2 * self.colormap_entries
+        return ctypes.string_at(self.colormap, n) if self.colormap and n else b""
+
+    def set_colormap(self, data: bytes) -> None:
+        """Point the layout at a copy of `data` (raw ColorMap values, two
+        bytes each in the byte order `big_endian` names) that lives as long
+        as it does."""
+        if len(data) % 2:
+            raise ValueError("a colormap holds 16-bit entries")
+        self._colormap_keep = (c_uint8 * max(1, len(data))).from_buffer_copy(data or b"\0")
+        self.colormap = ctypes.cast(self._colormap_keep, POINTER(c_uint8)) if data else None
+        self.colormap_entries = len(data) // 2
+
+    def copy_pixel_format(self, src: "Layout") -> None:
+        """Take `src`'s pixel-format fields, the colormap as a copy."""
+        self.photometric, self.fill_order = src.photometric, src.fill_order
+        self.set_colormap(src.colormap_bytes())
 
 
 class Stats(Structure):
@@ -91,7 +119,7 @@ class Stats(Structure):
 EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device_count", "jp2hip_device_ordinals",
            "jp2hip_recipe_init",
            "jp2hip_create", "jp2hip_destroy", "jp2hip_encode_file", "jp2hip_encode_tiff",
-           "jp2hip_tiff_layout", "jp2hip_file_header", "jp2hip_encode_device", "jp2hip_free",
+           "jp2hip_tiff_layout", "jp2hip_encoded_format", "jp2hip_file_header", "jp2hip_encode_device", "jp2hip_free",
            # batch path (csrc/batch.cpp; bound in jp2hip.batch)
            "jp2hip_batch_create", "jp2hip_batch_submit", "jp2hip_batch_wait", "jp2hip_batch_pending",
            "jp2hip_batch_destroy",
@@ -136,6 +164,7 @@ def lib():
                                      POINTER(POINTER(c_uint8)), POINTER(c_size_t), POINTER(Stats)]
     L.jp2hip_tiff_layout.argtypes = [c_void_p, c_size_t, POINTER(Layout), POINTER(c_uint64),
                                      c_int32]
+    L.jp2hip_encoded_format.argtypes = [POINTER(Layout), POINTER(c_int32), POINTER(c_int32)]
     L.jp2hip_file_header.argtypes = [POINTER(Layout), c_int32, c_uint64, c_void_p, c_size_t]
     L.jp2hip_file_header.restype = c_int64
     L.jp2hip_encode_device.argtypes = [c_void_p, c_void_p, c_size_t, POINTER(Layout), c_int,
@@ -245,7 +274,8 @@ def recipe(conversion: int, **overrides) -> Recipe:
 
 def tiff_layout(data: bytes):
     """Parse a baseline TIFF header; returns (Layout, offsets array).  The
-    Layout owns a copy of the file's ICC profile (Layout.icc points at it)."""
+    Layout owns copies of the file's ICC profile and ColorMap (Layout.icc and
+    Layout.colormap point at them)."""
     lay = Layout()
     cap = 1 << 20
     offs = (c_uint64 * cap)()
@@ -259,10 +289,21 @@ def tiff_layout(data: bytes):
     lay.strip_offsets = ctypes.cast(keep, POINTER(c_uint64))
     if packed:
         lay.strip_bytes = ctypes.cast(ctypes.byref(keep, 8 * n), POINTER(c_uint64))
-    # the library pointed lay.icc into `buf`, a temporary: re-point it at a
-    # copy the Layout keeps
+    # the library pointed lay.icc and lay.colormap into `buf`, a temporary:
+    # re-point them at copies the Layout keeps
     lay.set_icc_profile(lay.icc_profile())
+    lay.set_colormap(lay.colormap_bytes())
     return lay, keep
+
+
+def encoded_format(layout: Layout) -> tuple[int, int]:
+    """(components, bits) of the code-stream this source is encoded as
+    (jp2hip_encoded_format): 3 x 8 for a palette, 1 x 8 for 1-, 2- and 4-bit
+    grey, else the layout's own."""
+    nc, bits = c_int32(), c_int32()
+    if lib().jp2hip_encoded_format(byref(layout), byref(nc), byref(bits)) != 0:
+        raise Jp2hipError(last_error())
+    return int(nc.value), int(bits.value)
 
 
 def file_header(layout: Layout, fmt: int, codestream_bytes: int) -> bytes:

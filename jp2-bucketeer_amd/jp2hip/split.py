@@ -161,7 +161,8 @@ def band_strips(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
     rps, h, w = layout.rows_per_strip, layout.height, layout.width
     per_plane = (h + rps - 1) // rps
     planes = layout.components if layout.planar == 2 else 1
-    row_bytes = w * (1 if layout.planar == 2 else layout.components) * (layout.bits // 8)
+    # rows start on byte boundaries; samples below 8 bits are packed
+    row_bytes = (w * (1 if layout.planar == 2 else layout.components) * layout.bits + 7) // 8
     s0, s1 = row0 // rps, (row1 + rps - 1) // rps if row1 > row0 else row0 // rps
     new = (c_uint64 * (per_plane * planes))()
     chunks, pos = [], 0
@@ -177,6 +178,7 @@ def band_strips(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
                  layout.big_endian, layout.rows_per_strip, layout.nstrips,
                  ctypes.cast(new, POINTER(c_uint64)))
     lay.copy_metadata(layout)  # equal on every rank; rank 0 writes the file header from it
+    lay.copy_pixel_format(layout)
     return b"".join(chunks), lay, new
 
 
@@ -206,6 +208,7 @@ def _band_units(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
                  layout.compression, layout.predictor, ctypes.cast(ctypes.byref(new, 8 * n), POINTER(c_uint64)),
                  layout.tile_width, layout.tile_height)
     lay.copy_metadata(layout)
+    lay.copy_pixel_format(layout)
     return b"".join(chunks), lay, new
 
 
