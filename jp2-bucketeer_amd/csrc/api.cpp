@@ -6,6 +6,11 @@
 // same inputs (TIFF path, output path, Conversion), same recipe, blocking,
 // and every failure surfaces as a negative return code plus a message,
 // never as a partially written output file.
+//
+// Which bytes of a source hold the image -- the TIFF parser, the pixel-format
+// rules, the strip / tile grid and the bounds of the units a band of rows
+// reads -- is decided in source_layout.cpp (no HIP in it; the CPU suite runs
+// it under ASan / UBSan); prepare_source() below applies that to an encode.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +38,7 @@
 #include "jp2hip.h"
 #include "jp2hip_internal.h"
 #include "mem_policy.h"
+#include "source_layout.h"
 
 // The last geometry's plan, tier-2 tables and main-header length: a batch of
 // same-size images (the common case) builds them once (C2: ~5 ms of host
@@ -203,251 +209,15 @@ void out_free(void *p) {
     for (void *b : drop) (void)hipHostFree(b);
 }
 
+// The TIFF parser (source_layout.cpp), reporting as this file does.
+int read_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<uint64_t> &offs) {
+    std::string err;
+    return jp2hip::parse_tiff(buf, len, lay, offs, err) ? 0 : fail(err);
+}
+
 double now_ms() {
     using namespace std::chrono;
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
-// ---- baseline TIFF header parsing (tags 256-339; classic TIFF and BigTIFF) ----
-struct TiffReader {
-    const uint8_t *b;
-    size_t n;
-    bool le;
-    bool big = false;  // BigTIFF: 8-byte offsets, 20-byte IFD entries
-    uint64_t un(size_t o, int k) const {
-        if (o + (size_t)k > n || o + (size_t)k < o) return 0;
-        uint64_t v = 0;
-        for (int i = 0; i < k; i++) v |= (uint64_t)b[o + (le ? i : k - 1 - i)] << (8 * i);
-        return v;
-    }
-    uint32_t u16(size_t o) const { return (uint32_t)un(o, 2); }
-    uint32_t u32(size_t o) const { return (uint32_t)un(o, 4); }
-    uint64_t u64(size_t o) const { return un(o, 8); }
-    size_t entry_size() const { return big ? 20 : 12; }
-    uint64_t count(size_t e) const { return big ? u64(e + 4) : u32(e + 4); }
-    // value i of the entry at e (SHORT, LONG, LONG8 or BYTE)
-    uint64_t val(size_t e, uint64_t i) const {
-        const uint32_t type = u16(e + 2);
-        const uint64_t cnt = count(e);
-        const uint32_t sz = type == 3 ? 2 : (type == 4 ? 4 : (type == 16 ? 8 : 1));
-        const size_t inl = big ? 8 : 4, voff = big ? e + 12 : e + 8;
-        const uint64_t base = (uint64_t)sz * cnt <= inl ? voff : (big ? u64(voff) : u32(voff));
-        if (i >= cnt) return 0;
-        const size_t at = (size_t)(base + (uint64_t)sz * i);
-        return sz == 2 ? u16(at) : (sz == 4 ? u32(at) : (sz == 8 ? u64(at) : (at < n ? b[at] : 0)));
-    }
-    // Metadata tags (ICC profile, ExtraSamples, resolution): where the
-    // entry's `cnt` values of `sz` bytes lie, or false when they do not lie
-    // inside the file -- such a tag counts as absent, it never fails the parse.
-    bool data_at(size_t e, uint32_t sz, uint64_t cnt, size_t &at) const {
-        const size_t inl = big ? 8 : 4, voff = big ? e + 12 : e + 8;
-        if (cnt == 0 || cnt > n / sz) return false;
-        const uint64_t bytes = (uint64_t)sz * cnt;
-        const uint64_t base = bytes <= inl ? voff : (big ? u64(voff) : u32(voff));
-        if (base > n || bytes > n - base) return false;
-        at = (size_t)base;
-        return true;
-    }
-    // the first value of a RATIONAL entry (two LONGs: numerator, denominator)
-    bool rational(size_t e, uint32_t &num, uint32_t &den) const {
-        size_t at;
-        if (u16(e + 2) != 5 || !data_at(e, 8, count(e), at)) return false;
-        num = u32(at);
-        den = u32(at + 4);
-        return true;
-    }
-};
-
-// Bytes of a row of `w` pixels: rows start on byte boundaries, samples below
-// 8 bits are packed (TIFF 6.0 section 3 and 5).
-uint64_t packed_row_bytes(uint64_t w, uint64_t spp, uint64_t bits) { return (w * spp * bits + 7) / 8; }
-
-int parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<uint64_t> &offs) {
-    if (!buf || len < 8) return fail("tiff: input too short");
-    TiffReader t{buf, len, true};
-    if (buf[0] == 'I' && buf[1] == 'I') t.le = true;
-    else if (buf[0] == 'M' && buf[1] == 'M') t.le = false;
-    else return fail("tiff: bad byte-order mark");
-    size_t ifd, ifd_hdr;
-    if (t.u16(2) == 43) {  // BigTIFF: offset size 8, reserved 0, first IFD at 8
-        if (t.u16(4) != 8 || t.u16(6) != 0 || len < 16) return fail("tiff: bad BigTIFF header");
-        t.big = true;
-        ifd = (size_t)t.u64(8);
-        ifd_hdr = 8;
-    } else if (t.u16(2) == 42) {
-        ifd = t.u32(4);
-        ifd_hdr = 2;
-    } else {
-        return fail("tiff: not a TIFF file");
-    }
-    if (ifd + ifd_hdr > len || ifd + ifd_hdr < ifd) return fail("tiff: IFD offset out of range");
-    const uint64_t ne = t.big ? t.u64(ifd) : t.u16(ifd);
-    uint32_t w = 0, h = 0, spp = 1, bps = 8, comp = 1, planar = 1, rps = 0xFFFFFFFFu, fmt = 1, pred = 1;
-    uint32_t photo = 0xFFFFFFFFu;  // absent: inferred from SamplesPerPixel
-    uint32_t fill = 1;             // FillOrder: MSB-first when absent
-    size_t e_off = 0, e_cnt = 0, e_cmap = 0;
-    uint32_t n_off = 0, tw = 0, th = 0;
-    // what the file states about its pixels (the JP2 / JPX header carries it):
-    // a malformed one of these tags is an absent one
-    int32_t extra = 0;       // ExtraSamples value + 1; 0 absent
-    uint32_t res_unit = 2;   // ResolutionUnit: inch when absent
-    uint32_t xr[2] = {0, 0}, yr[2] = {0, 0};
-    const uint8_t *icc = nullptr;
-    uint64_t icc_bytes = 0;
-    if (ne > (len - ifd - ifd_hdr) / t.entry_size()) return fail("tiff: truncated IFD");
-    for (uint64_t i = 0; i < ne; i++) {
-        size_t e = ifd + ifd_hdr + t.entry_size() * (size_t)i;
-        switch (t.u16(e)) {
-        case 256: w = (uint32_t)t.val(e, 0); break;
-        case 257: h = (uint32_t)t.val(e, 0); break;
-        case 258: bps = (uint32_t)t.val(e, 0); break;
-        case 259: comp = (uint32_t)t.val(e, 0); break;
-        case 262: photo = (uint32_t)t.val(e, 0); break;
-        case 266: fill = (uint32_t)t.val(e, 0); break;
-        case 320: e_cmap = e; break;  // ColorMap
-        case 273: e_off = e; n_off = (uint32_t)std::min<uint64_t>(t.count(e), 0xFFFFFFFFu); break;
-        case 277: spp = (uint32_t)t.val(e, 0); break;
-        case 278: rps = (uint32_t)std::min<uint64_t>(t.val(e, 0), 0xFFFFFFFFu); break;
-        case 279: e_cnt = e; break;
-        case 284: planar = (uint32_t)t.val(e, 0); break;
-        case 317: pred = (uint32_t)t.val(e, 0); break;
-        case 322: tw = (uint32_t)t.val(e, 0); break;
-        case 323: th = (uint32_t)t.val(e, 0); break;
-        case 324: e_off = e; n_off = (uint32_t)std::min<uint64_t>(t.count(e), 0xFFFFFFFFu); break;  // TileOffsets
-        case 325: e_cnt = e; break;                                                                  // TileByteCounts
-        case 339: fmt = (uint32_t)t.val(e, 0); break;
-        case 282: if (!t.rational(e, xr[0], xr[1])) xr[0] = xr[1] = 0; break;  // XResolution
-        case 283: if (!t.rational(e, yr[0], yr[1])) yr[0] = yr[1] = 0; break;  // YResolution
-        case 296: {                                                            // ResolutionUnit
-            size_t at;
-            res_unit = (t.u16(e + 2) == 3 && t.data_at(e, 2, t.count(e), at)) ? t.u16(at) : 0;
-            break;
-        }
-        case 338: {  // ExtraSamples: the first value; an unknown one reads as 0 (unspecified)
-            size_t at;
-            extra = 0;
-            if (t.u16(e + 2) == 3 && t.data_at(e, 2, t.count(e), at)) extra = 1 + (int32_t)(t.u16(at) <= 2 ? t.u16(at) : 0);
-            break;
-        }
-        case 34675: {  // ICCProfile: recorded raw, classified when the header is written
-            size_t at;
-            const uint32_t type = t.u16(e + 2);
-            icc = nullptr;
-            icc_bytes = 0;
-            if ((type == 7 || type == 1) && t.data_at(e, 1, t.count(e), at)) {
-                icc = buf + at;
-                icc_bytes = t.count(e);
-            }
-            break;
-        }
-        default: break;
-        }
-    }
-    if (!w || !h || !e_off) return fail("tiff: missing ImageWidth/ImageLength/StripOffsets");
-    const bool tiled = tw || th;
-    if (tiled && (!tw || !th || (tw % 16) || (th % 16) || tw > 65536 || th > 65536))
-        return fail("tiff: bad TileWidth/TileLength");
-    if (tiled && !e_cnt) return fail("tiff: tiles need TileByteCounts");
-    // strips: uncompressed, LZW, Deflate or PackBits (decoded on the GPU,
-    // lzw.hip, unpack.hip k_inflate / k_unpackbits); JPEG / CCITT are not
-    if (comp != 1 && comp != 5 && comp != 8 && comp != 32946 && comp != 32773)
-        return fail("tiff: compression " + std::to_string(comp) +
-                    " is not supported (uncompressed, LZW, Deflate and PackBits only)");
-    if (pred != 1 && pred != 2) return fail("tiff: predictor " + std::to_string(pred) + " is not supported");
-    if (pred == 2 && comp == 1) return fail("tiff: predictor 2 without compression is not supported");
-    if (comp != 1 && !e_cnt) return fail("tiff: compressed strips need StripByteCounts");
-    if (bps != 1 && bps != 2 && bps != 4 && bps != 8 && bps != 16)
-        return fail("tiff: " + std::to_string(bps) + " bits/sample is not supported");
-    if (bps < 8 && spp != 1)
-        return fail("tiff: " + std::to_string(bps) + " bits/sample with " + std::to_string(spp) +
-                    " samples/pixel is not supported (packed samples: one per pixel only)");
-    if (bps < 8 && pred == 2)
-        return fail("tiff: predictor 2 with " + std::to_string(bps) + " bits/sample is not supported");
-    if (bps < 8 && fill != 1 && fill != 2) return fail("tiff: FillOrder " + std::to_string(fill) + " is not supported");
-    if (fmt != 1) return fail("tiff: only unsigned integer samples are supported");
-    if (spp < 1 || spp > 4) return fail("tiff: " + std::to_string(spp) + " samples/pixel is not supported");
-    if (planar != 1 && planar != 2) return fail("tiff: bad PlanarConfiguration");
-    // PhotometricInterpretation: BlackIsZero gray (+ alpha) or RGB (+ alpha);
-    // the colour transform assumes RGB in components 0..2
-    if (photo == 0xFFFFFFFFu) photo = spp >= 3 ? 2 : 1;
-    // WhiteIsZero: the 1-, 2- and 4-bit forms only (bilevel scans; expanded and
-    // inverted by k_expand)
-    if (photo == 0 && bps >= 8) return fail("tiff: PhotometricInterpretation 0 (WhiteIsZero) is not supported");
-    const uint8_t *cmap = nullptr;
-    if (photo == 3) {  // palette colour: indices of 1, 2, 4 or 8 bits and a whole ColorMap
-        if (spp != 1) return fail("tiff: PhotometricInterpretation 3 (palette) needs 1 sample/pixel");
-        if (bps > 8)
-            return fail("tiff: PhotometricInterpretation 3 (palette) with " + std::to_string(bps) +
-                        "-bit indices is not supported");
-        if (!e_cmap) return fail("tiff: PhotometricInterpretation 3 (palette) without a ColorMap is not supported");
-        size_t at;
-        if (t.u16(e_cmap + 2) != 3 || t.count(e_cmap) != (3ull << bps) || !t.data_at(e_cmap, 2, 3ull << bps, at))
-            return fail("tiff: PhotometricInterpretation 3 (palette): the ColorMap must be 3 * 2^" +
-                        std::to_string(bps) + " SHORTs inside the file");
-        cmap = buf + at;
-    } else if (photo != 0 && photo != 1 && photo != 2) {
-        return fail("tiff: PhotometricInterpretation " + std::to_string(photo) +
-                    " is not supported (gray, RGB or palette only)");
-    }
-    if (photo == 0 && spp != 1) return fail("tiff: WhiteIsZero with more than 1 sample/pixel is not supported");
-    if (photo == 2 && spp < 3) return fail("tiff: RGB needs 3 or 4 samples/pixel");
-    if (photo == 1 && spp > 2) return fail("tiff: BlackIsZero with more than 2 samples/pixel is not supported");
-    if (rps == 0 && !tiled) rps = h;  // RowsPerStrip 0 is invalid; libtiff reads it as one strip
-    if (rps > h) rps = h;
-    if (tiled) rps = th;  // per-unit rows (tiles are never clipped)
-    const uint32_t across = tiled ? (w + tw - 1) / tw : 1;
-    uint32_t per_plane = tiled ? across * ((h + th - 1) / th) : (h + rps - 1) / rps;
-    uint32_t need = per_plane * (planar == 2 ? spp : 1);
-    if (n_off < need) return fail(tiled ? "tiff: too few tiles" : "tiff: too few strips");
-    const bool packed = comp != 1 || tiled;
-    offs.resize(packed ? 2 * (size_t)need : need);
-    const size_t row = packed_row_bytes(w, planar == 2 ? 1 : spp, bps);
-    for (uint32_t s = 0; s < need; s++) {
-        offs[s] = t.val(e_off, s);
-        uint32_t y0 = (s % per_plane) * rps;
-        uint32_t rows = std::min(rps, h - y0);
-        if (packed) {
-            const uint64_t nb = t.val(e_cnt, s);
-            if (offs[s] > len || nb > len - offs[s]) return fail("tiff: strip " + std::to_string(s) + " out of range");
-            const uint64_t unit = packed_row_bytes(tw, planar == 2 ? 1 : spp, bps) * th;
-            if (tiled && comp == 1 && nb < unit) return fail("tiff: tile byte count too small");
-            offs[need + s] = nb;
-            continue;
-        }
-        if (offs[s] > len || (uint64_t)row * rows > len - offs[s])
-            return fail("tiff: strip " + std::to_string(s) + " out of range");
-        if (e_cnt && t.val(e_cnt, s) < row * rows) return fail("tiff: strip byte count too small");
-    }
-    lay->width = (int32_t)w;
-    lay->height = (int32_t)h;
-    lay->components = (int32_t)spp;
-    lay->bits = (int32_t)bps;
-    lay->planar = (int32_t)planar;
-    lay->big_endian = t.le ? 0 : 1;
-    lay->rows_per_strip = (int32_t)rps;
-    lay->nstrips = (int32_t)need;
-    lay->strip_offsets = offs.data();
-    lay->compression = (int32_t)comp;
-    lay->predictor = (int32_t)pred;
-    lay->strip_bytes = packed ? offs.data() + need : nullptr;
-    lay->tile_width = (int32_t)tw;
-    lay->tile_height = (int32_t)th;
-    // a resolution needs both rationals whole and a unit (1 "none" is kept
-    // as stated; the header writes a res box for inch and centimetre only)
-    const bool res = xr[0] && xr[1] && yr[0] && yr[1] && res_unit >= 1 && res_unit <= 3;
-    lay->extra_samples = extra;
-    lay->res_unit = res ? (int32_t)res_unit : 0;
-    lay->xres_num = res ? xr[0] : 0;
-    lay->xres_den = res ? xr[1] : 0;
-    lay->yres_num = res ? yr[0] : 0;
-    lay->yres_den = res ? yr[1] : 0;
-    lay->icc = icc;
-    lay->icc_bytes = icc_bytes;
-    lay->photometric = photo == 3 ? JP2HIP_PHOTO_PALETTE : (photo == 0 ? JP2HIP_PHOTO_WHITE_IS_ZERO : JP2HIP_PHOTO_DEFAULT);
-    lay->fill_order = bps < 8 ? (int32_t)fill : 0;
-    lay->colormap = cmap;
-    lay->colormap_entries = cmap ? (3ull << bps) : 0;
-    return 0;
 }
 
 void default_recipe(jp2hip_recipe *r, int conversion) {
@@ -481,321 +251,86 @@ int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h) {
     return (int64_t)std::floor(rc.rate_bpp * (double)w * (double)h / 8.0);
 }
 
-// Sources whose samples are expanded to 8 bits in HBM before ingest
-// (expand.hip): 1-, 2- and 4-bit grey and palette colour.
-bool needs_expand(const jp2hip_layout &lay) { return lay.bits < 8 || lay.photometric == JP2HIP_PHOTO_PALETTE; }
-
-// What the code-stream carries for this source (jp2hip_encoded_format).
-void encoded_format(const jp2hip_layout &lay, int &nc, int &bits) {
-    nc = lay.photometric == JP2HIP_PHOTO_PALETTE ? 3 : lay.components;
-    bits = needs_expand(lay) ? 8 : lay.bits;
-}
-
-// The pixel format of a layout, the parser's or a caller's: the depths,
-// component counts and photometric forms the encoder has a path for.
-bool check_pixel_format(const jp2hip_layout *lay, std::string &err) {
-    const int b = lay->bits;
-    if (b != 1 && b != 2 && b != 4 && b != 8 && b != 16) {
-        err = "layout: " + std::to_string(b) + " bits/sample is not supported";
-        return false;
-    }
-    if (lay->components < 1 || lay->components > 4 || (lay->planar != 1 && lay->planar != 2)) {
-        err = "layout: bad geometry or strip table";
-        return false;
-    }
-    if (lay->photometric != JP2HIP_PHOTO_DEFAULT && lay->photometric != JP2HIP_PHOTO_WHITE_IS_ZERO &&
-        lay->photometric != JP2HIP_PHOTO_PALETTE) {
-        err = "layout: unknown photometric " + std::to_string(lay->photometric);
-        return false;
-    }
-    if (b < 8 && lay->components != 1) {
-        err = "layout: samples below 8 bits need 1 component";
-        return false;
-    }
-    if (b < 8 && (lay->fill_order < 0 || lay->fill_order > 2)) {
-        err = "layout: fill_order must be 0, 1 or 2";
-        return false;
-    }
-    if (b < 8 && lay->predictor == 2) {
-        err = "layout: predictor 2 with samples below 8 bits is not supported";
-        return false;
-    }
-    if (lay->photometric == JP2HIP_PHOTO_WHITE_IS_ZERO && (b >= 8 || lay->components != 1)) {
-        err = "layout: photometric WhiteIsZero is supported for 1 component of 1, 2 or 4 bits only";
-        return false;
-    }
-    if (lay->photometric == JP2HIP_PHOTO_PALETTE &&
-        (b > 8 || lay->components != 1 || !lay->colormap || lay->colormap_entries != (3ull << b))) {
-        err = "layout: photometric palette needs 1 component of 1, 2, 4 or 8 bits and a colormap of 3 * 2^bits entries";
-        return false;
-    }
-    if (needs_expand(*lay) && lay->tile_width > 0 && lay->tile_width % 16) {
-        err = "layout: tiles of packed samples or palette indices need a tile_width in multiples of 16";
-        return false;
-    }
-    return true;
-}
-
-// The colour table of a palette layout as k_expand reads it: entry i is
-// R | G << 8 | B << 16.  ColorMap values are 16-bit (a component is the high
-// byte) unless no entry exceeds 255: such maps, from old writers, hold 8-bit
-// values and are taken as they are (libtiff's checkcmap).
-void palette_lut(const jp2hip_layout &lay, uint32_t *lut) {
-    const int n = 1 << lay.bits;
-    auto entry = [&](int i) -> uint32_t {
-        const uint8_t *p = lay.colormap + 2 * (size_t)i;
-        return lay.big_endian ? ((uint32_t)p[0] << 8) | p[1] : p[0] | ((uint32_t)p[1] << 8);
-    };
-    bool wide = false;
-    for (int i = 0; i < 3 * n; i++) wide = wide || entry(i) > 255;
-    const int sh = wide ? 8 : 0;
-    for (int i = 0; i < n; i++)
-        lut[i] = (entry(i) >> sh) | ((entry(n + i) >> sh) << 8) | ((entry(2 * n + i) >> sh) << 16);
-}
-
-// A caller-supplied layout (jp2hip_encode_device*) is checked against the
-// source buffer before any kernel reads it: the strips that rows [row0, row1)
-// touch must lie inside src_len (uncompressed), tiles must hold a whole tile
-// (uncompressed tiled), and compressed strips are checked in
-// unpack_if_compressed.
-bool validate_layout(const jp2hip_layout *lay, size_t src_len, int row0, int row1, std::string &err) {
-    if (lay->width <= 0 || lay->height <= 0 || lay->rows_per_strip <= 0 || lay->nstrips <= 0 || !lay->strip_offsets) {
-        err = "layout: bad geometry or strip table";
-        return false;
-    }
-    if (!check_pixel_format(lay, err)) return false;
-    const uint64_t spp_row = lay->planar == 2 ? 1 : (uint64_t)lay->components;
-    const int planes = lay->planar == 2 ? lay->components : 1;
-    if (lay->tile_width > 0 || lay->tile_height > 0) {
-        if (lay->tile_width <= 0 || lay->tile_height <= 0 || !lay->strip_bytes) {
-            err = "layout: tiles need tile_width, tile_height and strip_bytes";
-            return false;
-        }
-        const int64_t across = (lay->width + lay->tile_width - 1) / lay->tile_width;
-        const int64_t need = across * ((lay->height + lay->tile_height - 1) / lay->tile_height) * planes;
-        if (need > lay->nstrips) { err = "layout: too few tiles"; return false; }
-        const uint64_t unit = packed_row_bytes(lay->tile_width, spp_row, lay->bits) * lay->tile_height;
-        for (int64_t i = 0; i < need; i++) {
-            const uint64_t o = lay->strip_offsets[i], n = lay->strip_bytes[i];
-            if (o > src_len || n > src_len - o || (lay->compression <= 1 && n < unit)) {
-                err = "layout: tile " + std::to_string(i) + " lies outside the source buffer or is short";
-                return false;
-            }
-        }
-        return true;
-    }
-    if (lay->compression > 1) return true;  // checked with the strip byte counts in unpack_if_compressed
-    const int64_t per_plane = (lay->height + (int64_t)lay->rows_per_strip - 1) / lay->rows_per_strip;
-    if (per_plane * planes > lay->nstrips) { err = "layout: too few strips"; return false; }
-    const uint64_t row_bytes = packed_row_bytes(lay->width, spp_row, lay->bits);
-    const int64_t s0 = std::max(0, row0) / lay->rows_per_strip;
-    const int64_t s1 = std::min<int64_t>(per_plane, ((int64_t)std::min(row1, lay->height) + lay->rows_per_strip - 1) /
-                                                        lay->rows_per_strip);
-    for (int p = 0; p < planes; p++)
-        for (int64_t s = s0; s < s1; s++) {
-            const uint64_t o = lay->strip_offsets[(size_t)(p * per_plane + s)];
-            const uint64_t rows = (uint64_t)std::min<int64_t>(lay->rows_per_strip, lay->height - s * lay->rows_per_strip);
-            if (o > src_len || rows * row_bytes > src_len - o) {
-                err = "layout: strip " + std::to_string(p * per_plane + s) + " lies outside the source buffer";
-                return false;
-            }
-        }
-    return true;
-}
-
-// LZW / Deflate / PackBits strips are decoded on the GPU into the context's staging
-// buffer first; afterwards (d_src, lay) describe uncompressed strips.
-bool unpack_if_compressed(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2hip_layout *&lay,
-                          jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err) {
-    if (lay->compression <= 1 && lay->tile_width <= 0) return true;
-    if (lay->compression > 1 && lay->compression != 5 && lay->compression != 8 && lay->compression != 32946 &&
-        lay->compression != 32773) {
-        err = "layout: compression " + std::to_string(lay->compression) + " is not supported";
-        return false;
-    }
-    if (!lay->strip_bytes || !lay->strip_offsets || lay->nstrips <= 0 || lay->rows_per_strip <= 0 ||
-        (lay->tile_width > 0) != (lay->tile_height > 0)) {
-        err = "layout: compressed strips / tiles need strip_offsets and strip_bytes";
-        return false;
-    }
-    for (int i = 0; i < lay->nstrips; i++)  // the decoders trust these bounds
-        if (lay->strip_offsets[i] > src_len || lay->strip_bytes[i] > src_len - lay->strip_offsets[i]) {
-            err = "layout: compressed strip " + std::to_string(i) + " lies outside the source buffer";
-            return false;
-        }
-    const void *d2 = nullptr;
-    if (!ctx->gpu.unpack_strips(d_src, *lay, ulay, uoffs, &d2, err)) return false;
-    d_src = d2;
-    lay = &ulay;
-    return true;
-}
-
-// Tile-split with compressed or tiled strips (a rank's band of a BigTIFF
-// master): only the strips / tiles that image rows [row0, row1) touch are
-// decoded -- as a stand-alone image of their rows [R0, R1) -- and the result
-// is described as a full-image layout of uncompressed strips whose entries
-// outside the band are never read (the sub-plan reads only its rows).  Only
-// the band's units must lie inside d_src, as for uncompressed strips.
-bool unpack_band(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2hip_layout *&lay, int row0, int row1,
-                 jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err) {
-    if (lay->compression <= 1 && lay->tile_width <= 0) return true;
-    const bool tiled = lay->tile_width > 0;
-    if (lay->width <= 0 || lay->height <= 0 || !lay->strip_offsets || !lay->strip_bytes ||
-        (tiled && lay->tile_height <= 0) || (!tiled && lay->rows_per_strip <= 0)) {
-        err = "layout: compressed strips / tiles need a geometry, strip_offsets and strip_bytes";
-        return false;
-    }
-    if (!check_pixel_format(lay, err)) return false;
-    const int uh = tiled ? lay->tile_height : lay->rows_per_strip;  // rows per unit
-    const int planes = lay->planar == 2 ? lay->components : 1;
-    const int64_t across = tiled ? (lay->width + lay->tile_width - 1) / lay->tile_width : 1;
-    const int64_t urows = (lay->height + (int64_t)uh - 1) / uh;  // unit rows per plane
-    const int64_t per_plane = across * urows;
-    if (per_plane * planes > lay->nstrips) {
-        err = tiled ? "layout: too few tiles" : "layout: too few strips";
-        return false;
-    }
-    const int64_t u0 = std::max(0, row0) / uh;
-    const int64_t u1 = std::min<int64_t>(urows, ((int64_t)std::min(row1, lay->height) + uh - 1) / uh);
-    if (u1 <= u0) {
-        err = "layout: empty band";
-        return false;
-    }
-    const int R0 = (int)(u0 * uh), R1 = (int)std::min<int64_t>(lay->height, u1 * uh);
-    const uint64_t spp_row = lay->planar == 2 ? 1 : (uint64_t)lay->components;
-    const uint64_t unit = tiled ? packed_row_bytes(lay->tile_width, spp_row, lay->bits) * lay->tile_height : 0;
+// What every encode does to its source before the front: the units (strips
+// or tiles; source_layout.h) that image rows [row0, row1) touch are checked
+// against src_len -- they alone must lie inside d_src, so a tile-split rank
+// passes its band -- and, unless they are uncompressed strips of whole
+// samples, which ingest reads in place, brought to that form in HBM as a
+// stand-alone image of the band's rows: decoded (S1a: LZW / Deflate /
+// PackBits, tiles untiled), then, for 1-, 2-, 4-bit samples and palette
+// indices, expanded to 8 bits (S1b; such tiles stay tiles when decoded, the
+// expansion untiles).  Afterwards (d_src, lay) describe the whole image as
+// uncompressed strips whose entries outside the band are never read (the
+// plan, or a rank's sub-plan, reads only its rows).
+bool prepare_source(jp2hip_ctx *ctx, const jp2hip::UnitGrid &g, const void *&d_src, size_t src_len,
+                    const jp2hip_layout *&lay, int row0, int row1, jp2hip_layout &ulay, std::vector<uint64_t> &uoffs,
+                    std::string &err) {
+    using namespace jp2hip;
+    Band band;
+    if (!band_walk(*lay, g, row0, row1, src_len, band, err)) return false;
+    const bool expand = needs_expand(*lay);
+    if (!g.tiled && !g.coded && !expand) return true;
     std::vector<uint64_t> voff, vcnt;
-    for (int p = 0; p < planes; p++)
-        for (int64_t u = u0; u < u1; u++)
-            for (int64_t x = 0; x < across; x++) {
-                const size_t i = (size_t)(p * per_plane + u * across + x);
-                const uint64_t o = lay->strip_offsets[i], n = lay->strip_bytes[i];
-                if (o > src_len || n > src_len - o || (lay->compression <= 1 && n < unit)) {
-                    err = "layout: strip / tile " + std::to_string(i) + " of the band lies outside the source buffer";
-                    return false;
-                }
-                voff.push_back(o);
-                vcnt.push_back(n);
-            }
+    for (const BandUnit &u : band.units) {
+        voff.push_back(u.off);
+        vcnt.push_back(u.bytes);
+    }
     jp2hip_layout v = *lay;
-    v.height = R1 - R0;
+    v.height = (int32_t)(band.row1 - band.row0);
     v.nstrips = (int32_t)voff.size();
     v.strip_offsets = voff.data();
     v.strip_bytes = vcnt.data();
-    jp2hip_layout vu;
-    std::vector<uint64_t> vuoffs;
-    const void *d2 = nullptr;
-    if (!ctx->gpu.unpack_strips(d_src, v, vu, vuoffs, &d2, err)) return false;
-    // the full-image view: unit row u of plane p at its decoded place
-    const uint64_t row_bytes = packed_row_bytes(lay->width, spp_row, lay->bits);
-    ulay = vu;
-    ulay.height = lay->height;
-    ulay.rows_per_strip = uh;
-    ulay.nstrips = (int32_t)(urows * planes);
-    uoffs.assign((size_t)(urows * planes), 0);
-    for (int p = 0; p < planes; p++)
-        for (int64_t u = u0; u < u1; u++)
-            uoffs[(size_t)(p * urows + u)] = tiled ? vuoffs[(size_t)p] + (uint64_t)(u - u0) * uh * row_bytes
-                                                   : vuoffs[(size_t)(p * (u1 - u0) + (u - u0))];
-    ulay.strip_offsets = uoffs.data();
-    d_src = d2;
-    lay = &ulay;
-    return true;
-}
-
-// S1b: a source of 1-, 2-, 4-bit samples or palette indices (needs_expand)
-// becomes 8-bit samples in HBM.  Only the units (strips or tiles) that image
-// rows [row0, row1) touch are read -- they alone must lie inside d_src, so a
-// tile-split rank passes its band -- decoded first when they are compressed
-// (as tiles they stay tiles: the expansion untiles), then expanded into a
-// copy sized by those rows.  Afterwards (d_src, lay) describe the whole
-// image as uncompressed 8-bit strips, grey or chunky RGB, of which the
-// entries outside the band are never read (as after unpack_band).
-bool expand_source(jp2hip_ctx *ctx, const void *&d_src, size_t src_len, const jp2hip_layout *&lay, int row0, int row1,
-                   jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err) {
-    const bool tiled = lay->tile_width > 0 || lay->tile_height > 0, decode = lay->compression > 1;
-    if (lay->width <= 0 || lay->height <= 0 || !lay->strip_offsets || lay->nstrips <= 0 ||
-        (tiled && (lay->tile_width <= 0 || lay->tile_height <= 0)) || (!tiled && lay->rows_per_strip <= 0) ||
-        ((tiled || decode) && !lay->strip_bytes)) {
-        err = "layout: bad geometry or strip table (compressed strips and tiles need strip_bytes)";
-        return false;
-    }
-    if (!check_pixel_format(lay, err)) return false;
-    if (decode && lay->compression != 5 && lay->compression != 8 && lay->compression != 32946 &&
-        lay->compression != 32773) {
-        err = "layout: compression " + std::to_string(lay->compression) + " is not supported";
-        return false;
-    }
-    const int uh = tiled ? lay->tile_height : lay->rows_per_strip;  // rows per unit
-    const int64_t across = tiled ? (lay->width + (int64_t)lay->tile_width - 1) / lay->tile_width : 1;
-    const int64_t urows = (lay->height + (int64_t)uh - 1) / uh;
-    if (across * urows > lay->nstrips) {
-        err = tiled ? "layout: too few tiles" : "layout: too few strips";
-        return false;
-    }
-    const int64_t u0 = std::max(0, row0) / uh;
-    const int64_t u1 = std::min<int64_t>(urows, ((int64_t)std::min(row1, lay->height) + uh - 1) / uh);
-    if (u1 <= u0) {
-        err = "layout: empty band";
-        return false;
-    }
-    const int R0 = (int)(u0 * uh), R1 = (int)std::min<int64_t>(lay->height, u1 * uh);
-    const uint64_t unit_row = packed_row_bytes(tiled ? lay->tile_width : lay->width, 1, lay->bits);
-    std::vector<uint64_t> voff, vcnt;
-    for (int64_t u = u0; u < u1; u++)
-        for (int64_t x = 0; x < across; x++) {
-            const size_t i = (size_t)(u * across + x);
-            const uint64_t o = lay->strip_offsets[i];
-            // what the expansion reads of an uncompressed unit; a compressed one is read whole
-            const uint64_t rows = tiled ? (uint64_t)uh : (uint64_t)std::min<int64_t>(uh, lay->height - u * uh);
-            const uint64_t n = lay->strip_bytes ? lay->strip_bytes[i] : rows * unit_row;
-            if (o > src_len || n > src_len - o || (!decode && n < rows * unit_row)) {
-                err = "layout: strip / tile " + std::to_string(i) + " lies outside the source buffer or is short";
-                return false;
-            }
-            voff.push_back(o);
-            vcnt.push_back(n);
-        }
-    jp2hip_layout v = *lay;
-    v.height = R1 - R0;
-    v.nstrips = (int32_t)voff.size();
-    v.strip_offsets = voff.data();
-    v.strip_bytes = vcnt.data();
+    UnitGrid gv;
+    if (!unit_grid(v, gv, err)) return false;
     jp2hip_layout vu;
     std::vector<uint64_t> vuoffs;
     const jp2hip_layout *cur = &v;
     const void *d = d_src;
-    if (decode) {
-        if (!ctx->gpu.unpack_strips(d_src, v, vu, vuoffs, &d, err, false)) return false;
+    if (g.coded || !expand) {
+        if (!ctx->gpu.unpack_strips(d_src, v, gv, vu, vuoffs, &d, err, !expand)) return false;
         cur = &vu;
     }
-    // the colour table: per encode, never with the cached plan (two files of
-    // one geometry have their own maps)
-    uint32_t lut[256];
-    const bool palette = lay->photometric == JP2HIP_PHOTO_PALETTE;
-    if (palette) palette_lut(*lay, lut);
-    const void *d8 = nullptr;
-    if (!ctx->gpu.expand_samples(d, *cur, R1 - R0, palette ? lut : nullptr, ctx->cfg.profile != 0, &d8, err)) return false;
     int nc, bits;
     encoded_format(*lay, nc, bits);
+    if (expand) {
+        // the colour table: per encode, never with the cached plan (two files
+        // of one geometry have their own maps)
+        uint32_t lut[256];
+        const bool palette = lay->photometric == JP2HIP_PHOTO_PALETTE;
+        if (palette) palette_lut(*lay, lut);
+        if (!ctx->gpu.expand_samples(d, *cur, gv, palette ? lut : nullptr, ctx->cfg.profile != 0, &d, err)) return false;
+    }
+    // the full-image view: unit row u of plane p at its place in the copy
+    // (decoded strips stand one per table entry; untiled or expanded rows
+    // are row-major per plane)
+    const int64_t nu = band.u1 - band.u0;
+    const uint64_t img_row = expand ? (uint64_t)lay->width * nc
+                                    : packed_row_bytes(lay->width, lay->planar == 2 ? 1 : lay->components, lay->bits);
+    uoffs.assign((size_t)(g.urows * g.planes), 0);
+    for (int64_t p = 0; p < g.planes; p++)
+        for (int64_t u = band.u0; u < band.u1; u++)
+            uoffs[(size_t)(p * g.urows + u)] =
+                expand    ? (uint64_t)(u - band.u0) * g.unit_h * img_row
+                : g.tiled ? vuoffs[(size_t)p] + (uint64_t)(u - band.u0) * g.unit_h * img_row
+                          : vuoffs[(size_t)(p * nu + (u - band.u0))];
     ulay = *lay;
-    ulay.components = nc;
-    ulay.bits = bits;
-    ulay.planar = 1;
-    ulay.rows_per_strip = uh;
-    ulay.nstrips = (int32_t)urows;
+    ulay.rows_per_strip = (int32_t)g.unit_h;
+    ulay.nstrips = (int32_t)(g.urows * g.planes);
+    ulay.strip_offsets = uoffs.data();
     ulay.compression = 1;
     ulay.predictor = 1;
     ulay.strip_bytes = nullptr;
     ulay.tile_width = ulay.tile_height = 0;
-    ulay.photometric = JP2HIP_PHOTO_DEFAULT;
-    ulay.fill_order = 0;
-    ulay.colormap = nullptr;
-    ulay.colormap_entries = 0;
-    uoffs.assign((size_t)urows, 0);
-    for (int64_t u = u0; u < u1; u++) uoffs[(size_t)u] = (uint64_t)(u - u0) * uh * lay->width * nc;
-    ulay.strip_offsets = uoffs.data();
-    d_src = d8;
+    if (expand) {  // 8-bit grey or chunky RGB
+        ulay.components = nc;
+        ulay.bits = bits;
+        ulay.planar = 1;
+        ulay.photometric = JP2HIP_PHOTO_DEFAULT;
+        ulay.fill_order = 0;
+        ulay.colormap = nullptr;
+        ulay.colormap_entries = 0;
+    }
+    d_src = d;
     lay = &ulay;
     return true;
 }
@@ -873,9 +408,8 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     std::string err;
     jp2hip_layout ulay;
     std::vector<uint64_t> uoffs;
-    if (!validate_layout(lay, src_len, 0, lay->height, err)) return fail(err);
-    if (needs_expand(*lay) ? !expand_source(ctx, d_src, src_len, lay, 0, lay->height, ulay, uoffs, err)
-                           : !unpack_if_compressed(ctx, d_src, src_len, lay, ulay, uoffs, err))
+    UnitGrid grid;
+    if (!unit_grid(*lay, grid, err) || !prepare_source(ctx, grid, d_src, src_len, lay, 0, lay->height, ulay, uoffs, err))
         return fail(err);
     PlanCache &pc = ctx->pc;
     if (!pc.valid || pc.w != lay->width || pc.h != lay->height || pc.nc != lay->components || pc.bits != lay->bits ||
@@ -1018,7 +552,8 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     EncodeEnd end{ctx};
     Plan full;
     std::string err;
-    if (!check_pixel_format(lay, err)) return fail(err);
+    UnitGrid grid;  // (the same on every rank: a layout it refuses fails them all here)
+    if (!unit_grid(*lay, grid, err)) return fail(err);
     int enc_nc, enc_bits;  // the plan sees what the code-stream carries
     encoded_format(*lay, enc_nc, enc_bits);
     if (!build_plan(full, rc, lay->width, lay->height, enc_nc, enc_bits, err)) return fail(err);
@@ -1032,11 +567,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // that fails here still joins every exchange below)
     jp2hip_layout ulay;
     std::vector<uint64_t> uoffs;
-    const bool packed = lay->compression > 1 || lay->tile_width > 0;
-    bool ok = !have ||
-              (needs_expand(*lay) ? expand_source(ctx, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err)
-               : packed           ? unpack_band(ctx, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err)
-                                  : validate_layout(lay, src_len, sub.row0, sub.row0 + sub.band_h, err));
+    bool ok = !have || prepare_source(ctx, grid, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err);
     const bool prof = ctx->cfg.profile != 0;
     StageTimes st;
     std::vector<uint64_t> keys;
@@ -1288,48 +819,6 @@ class HostGroup {
     std::vector<int64_t> acc_, res_[2];
 };
 
-// The strips (or compressed strips / tiles, whole) that image rows
-// [row0, row1) read, as (file offset, bytes, strip-table index): what one rank
-// uploads.  The C++ form of jp2hip.split.band_strips.
-struct BandCopy {
-    uint64_t src, n;
-    size_t idx;
-};
-bool band_units(const jp2hip_layout &lay, size_t flen, int row0, int row1, std::vector<BandCopy> &cp,
-                std::string &err) {
-    cp.clear();
-    if (row1 <= row0) return true;
-    const bool packed = lay.compression > 1 || lay.tile_width > 0, tiled = lay.tile_width > 0;
-    const int uh = tiled ? lay.tile_height : lay.rows_per_strip;
-    if (uh <= 0 || lay.width <= 0 || lay.height <= 0 || (packed && !lay.strip_bytes) || !lay.strip_offsets) {
-        err = "layout: bad strip table";
-        return false;
-    }
-    const int planes = lay.planar == 2 ? lay.components : 1;
-    const int64_t across = tiled ? (lay.width + (int64_t)lay.tile_width - 1) / lay.tile_width : 1;
-    const int64_t urows = (lay.height + (int64_t)uh - 1) / uh, per_plane = across * urows;
-    if (per_plane * planes > lay.nstrips) {
-        err = tiled ? "layout: too few tiles" : "layout: too few strips";
-        return false;
-    }
-    const uint64_t row_bytes = packed_row_bytes(lay.width, lay.planar == 2 ? 1 : lay.components, lay.bits);
-    const int64_t u0 = row0 / uh, u1 = std::min<int64_t>(urows, (row1 + (int64_t)uh - 1) / uh);
-    for (int p = 0; p < planes; p++)
-        for (int64_t u = u0; u < u1; u++)
-            for (int64_t x = 0; x < across; x++) {
-                const size_t i = (size_t)(p * per_plane + u * across + x);
-                const uint64_t o = lay.strip_offsets[i];
-                const uint64_t n = packed ? lay.strip_bytes[i]
-                                          : (uint64_t)std::min<int64_t>(uh, lay.height - u * uh) * row_bytes;
-                if (o > flen || n > flen - o) {
-                    err = "tiff: strip " + std::to_string(i) + " out of range";
-                    return false;
-                }
-                cp.push_back({o, n, i});
-            }
-    return true;
-}
-
 struct RankResult {
     int rc = -1;
     std::string err;
@@ -1348,27 +837,30 @@ void split_rank(jp2hip_ctx *m, int rank, int world, HostGroup &grp, const uint8_
     std::memset(&o.st, 0, sizeof o.st);
     int r0 = 0, r1 = 0;
     jp2hip_split_rows(lay.height, rc.tile_h, rc.flush_period, rank, world, &r0, &r1);
-    std::vector<BandCopy> cp;
-    if (!band_units(lay, flen, r0, r1, cp, o.err)) {
+    // what this rank uploads: the units its rows read, whole (the C++ form
+    // of jp2hip.split.band_strips)
+    jp2hip::UnitGrid grid;
+    jp2hip::Band band;
+    if (!jp2hip::unit_grid(lay, grid, o.err) || !jp2hip::band_walk(lay, grid, r0, r1, flen, band, o.err)) {
         grp.abort();
         return;
     }
     size_t tot = 0;
-    for (const BandCopy &c : cp) tot += c.n;
+    for (const jp2hip::BandUnit &c : band.units) tot += c.bytes;
     uint8_t *h = out_alloc(std::max<size_t>(tot, 1));  // pinned: the upload is one DMA
     if (!h) {
         o.err = "out of (pinned) host memory";
         grp.abort();
         return;
     }
-    const bool packed = lay.compression > 1 || lay.tile_width > 0;
+    const bool packed = grid.coded || grid.tiled;
     std::vector<uint64_t> offs((size_t)lay.nstrips * (packed ? 2 : 1), 0);
     size_t pos = 0;
-    for (const BandCopy &c : cp) {
-        std::memcpy(h + pos, file + c.src, c.n);
+    for (const jp2hip::BandUnit &c : band.units) {
+        std::memcpy(h + pos, file + c.off, c.bytes);
         offs[c.idx] = pos;
-        if (packed) offs[(size_t)lay.nstrips + c.idx] = c.n;
-        pos += c.n;
+        if (packed) offs[(size_t)lay.nstrips + c.idx] = c.bytes;
+        pos += c.bytes;
     }
     jp2hip_layout bl = lay;
     bl.strip_offsets = offs.data();
@@ -1660,7 +1152,7 @@ int jp2hip_tiff_layout(const uint8_t *tiff, size_t len, jp2hip_layout *layout, u
                        int32_t max_offsets) {
     if (!layout) return fail("null layout");
     std::vector<uint64_t> offs;
-    if (parse_tiff(tiff, len, layout, offs)) return -1;
+    if (read_tiff(tiff, len, layout, offs)) return -1;
     if ((int32_t)offs.size() > max_offsets || !offsets) {
         layout->strip_offsets = nullptr;
         return fail("offsets array too small: need " + std::to_string(offs.size()));
@@ -1674,7 +1166,7 @@ int jp2hip_tiff_layout(const uint8_t *tiff, size_t len, jp2hip_layout *layout, u
 int jp2hip_encoded_format(const jp2hip_layout *layout, int32_t *components, int32_t *bits) {
     if (!layout || !components || !bits) return fail("null argument");
     int nc, b;
-    encoded_format(*layout, nc, b);
+    jp2hip::encoded_format(*layout, nc, b);
     *components = nc;
     *bits = b;
     return 0;
@@ -1691,7 +1183,7 @@ int64_t jp2hip_file_header(const jp2hip_layout *layout, int32_t format, uint64_t
     hdr.rc.format = format;
     hdr.w = layout->width;
     hdr.h = layout->height;
-    encoded_format(*layout, hdr.nc, hdr.bits);
+    jp2hip::encoded_format(*layout, hdr.nc, hdr.bits);
     const jp2hip::SourceMeta meta = jp2hip::source_meta(*layout);
     const size_t n = jp2hip::file_header_bytes(hdr, meta);
     if (n && dst && cap >= n) jp2hip::write_file_header(hdr, meta, codestream_bytes, dst);
@@ -1717,7 +1209,7 @@ int jp2hip_encode_tiff(jp2hip_ctx *ctx, const uint8_t *tiff, size_t len, int con
     double t0 = now_ms();
     jp2hip_layout lay;
     std::vector<uint64_t> offs;
-    if (parse_tiff(tiff, len, &lay, offs)) return -1;
+    if (read_tiff(tiff, len, &lay, offs)) return -1;
     if (wants_split(ctx, lay))
         return encode_split_host(ctx, tiff, len, lay, conversion, recipe, -1, out, out_len, stats, t0);
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -1739,7 +1231,7 @@ int jp2hip_encode_file(jp2hip_ctx *ctx, const char *tiff_path, const char *out_p
     }
     jp2hip_layout lay;
     std::vector<uint64_t> offs;
-    if (parse_tiff(mf.p, mf.n, &lay, offs)) return -1;
+    if (read_tiff(mf.p, mf.n, &lay, offs)) return -1;
     const std::string tmp = temp_name(out_path);
     if (wants_split(ctx, lay)) {
         // every rank writes its part at its offset of the temp file
@@ -1778,7 +1270,7 @@ int64_t jp2hip_tiff_pixels(const char *tiff_path) {
     if (!mf.open(tiff_path)) return fail(std::string("cannot open TIFF: ") + tiff_path);
     jp2hip_layout lay;
     std::vector<uint64_t> offs;
-    if (parse_tiff(mf.p, mf.n, &lay, offs)) return -1;
+    if (read_tiff(mf.p, mf.n, &lay, offs)) return -1;
     return (int64_t)lay.width * lay.height;
 }
 

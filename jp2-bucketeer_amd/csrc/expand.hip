@@ -132,19 +132,17 @@ bool launch_expand(const ExpandArgs &a, int bits, bool palette, hipStream_t st) 
     return hipGetLastError() == hipSuccess;
 }
 
-// `lay` describes uncompressed units (strips or tiles, one sample per pixel)
-// in d_src; its `rows` rows are expanded into this context's `expanded`
+// `lay` describes uncompressed units (strips or tiles of grid `g`, one sample
+// per pixel) in d_src; its rows are expanded into this context's `expanded`
 // buffer.  lut: 2^bits dwords for a palette, else nullptr.  The offset table
 // and the colour table go through the pinned staging like every host ->
 // device copy of an encode; nothing here waits for the GPU.
-bool GpuEncoder::expand_samples(const void *d_src, const jp2hip_layout &lay, int rows, const uint32_t *lut,
+bool GpuEncoder::expand_samples(const void *d_src, const jp2hip_layout &lay, const UnitGrid &g, const uint32_t *lut,
                                 bool profile, const void **d_out, std::string &err) {
     HIPCHECK(hipSetDevice(device));
-    const bool tiled = lay.tile_width > 0, palette = lut != nullptr;
-    const int unit_w = tiled ? lay.tile_width : lay.width, unit_h = tiled ? lay.tile_height : lay.rows_per_strip;
-    const int across = tiled ? (lay.width + unit_w - 1) / unit_w : 1;
-    const int units = across * ((rows + unit_h - 1) / unit_h);
-    if (units > lay.nstrips || lay.bits > 8 || (tiled && unit_w % kExpandPx)) {
+    const bool palette = lut != nullptr;
+    const int rows = lay.height, unit_w = (int)g.unit_w, unit_h = (int)g.unit_h, units = (int)g.needed;
+    if (g.planes != 1 || units > lay.nstrips || lay.bits > 8 || (g.tiled && unit_w % kExpandPx)) {
         err = "layout: sample expansion needs one unit per strip / tile of its rows and tile widths in multiples of 16";
         return false;
     }
@@ -161,8 +159,8 @@ bool GpuEncoder::expand_samples(const void *d_src, const jp2hip_layout &lay, int
     a.rows = rows;
     a.unit_w = unit_w;
     a.unit_h = unit_h;
-    a.across = across;
-    a.row_bytes = (uint32_t)(((uint64_t)unit_w * lay.bits + 7) / 8);
+    a.across = (int)g.across;
+    a.row_bytes = (uint32_t)g.row_bytes;
     a.lsb_first = lay.fill_order == 2 && lay.bits < 8;
     a.invert = lay.photometric == JP2HIP_PHOTO_WHITE_IS_ZERO ? 0xFFFFFFFFu : 0u;
     a.lut = (const uint32_t *)exlut.ptr;

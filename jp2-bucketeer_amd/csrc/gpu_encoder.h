@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "jp2hip_internal.h"
+#include "source_layout.h"
 #include "stages.h"
 
 namespace jp2hip {
@@ -102,15 +103,18 @@ class GpuEncoder {
     // LZW / PackBits strips (+ Predictor 2) -> an uncompressed staging copy
     // in HBM; `out` describes it (offsets in out_offs).  untile = false
     // (sources that expand_samples reads next, which untiles itself): decoded
-    // tiles stay tiles, one per entry of out_offs
-    bool unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2hip_layout &out,
+    // tiles stay tiles, one per entry of out_offs.  `g` is lay's grid
+    // (source_layout.h unit_grid): lay's table holds exactly the units of
+    // its height, each checked against the source (api.cpp prepare_source)
+    bool unpack_strips(const void *d_src, const jp2hip_layout &lay, const UnitGrid &g, jp2hip_layout &out,
                        std::vector<uint64_t> &out_offs, const void **d_out, std::string &err, bool untile = true);
 
-    // S1b (expand.hip): `rows` rows of uncompressed 1-, 2-, 4-bit samples or
-    // palette indices (lut: 2^bits packed colours, else nullptr) -> 8-bit
-    // samples in the `expanded` buffer, one row-major strip; enqueued only
-    bool expand_samples(const void *d_src, const jp2hip_layout &lay, int rows, const uint32_t *lut, bool profile,
-                        const void **d_out, std::string &err);
+    // S1b (expand.hip): the rows of `lay` -- uncompressed 1-, 2-, 4-bit
+    // samples or palette indices (lut: 2^bits packed colours, else nullptr)
+    // in units of grid `g` -> 8-bit samples in the `expanded` buffer, one
+    // row-major strip; enqueued only
+    bool expand_samples(const void *d_src, const jp2hip_layout &lay, const UnitGrid &g, const uint32_t *lut,
+                        bool profile, const void **d_out, std::string &err);
 
     // Sums a slope-prediction histogram over the ranks of a tile-split
     // encode, in place; false = exchange failed (or another rank failed).

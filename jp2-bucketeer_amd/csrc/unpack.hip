@@ -95,25 +95,21 @@ __global__ void __launch_bounds__(256) k_untile(const uint8_t *base, const uint6
     for (int i = 0; i < px_bytes; i++) dst[i] = src[i];
 }
 
-bool GpuEncoder::unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2hip_layout &out,
+bool GpuEncoder::unpack_strips(const void *d_src, const jp2hip_layout &lay, const UnitGrid &g, jp2hip_layout &out,
                                std::vector<uint64_t> &out_offs, const void **d_out, std::string &err,
                                bool untile) {
     HIPCHECK(hipSetDevice(device));
-    const int ns = lay.nstrips;  // strips, or tiles
-    const bool tiled = lay.tile_width > 0;
+    const int ns = (int)g.needed;  // strips, or tiles
+    const bool tiled = g.tiled;
     const int spp_row = lay.planar == 2 ? 1 : lay.components;
     const int px_bytes = spp_row * (lay.bits / 8);  // (0 below 8 bits: such tiles are not untiled here)
-    const int unit_w = tiled ? lay.tile_width : lay.width, unit_h = tiled ? lay.tile_height : lay.rows_per_strip;
-    const int planes = lay.planar == 2 ? lay.components : 1;
-    const int across = tiled ? (lay.width + lay.tile_width - 1) / lay.tile_width : 1;
-    const int per_plane = tiled ? across * ((lay.height + lay.tile_height - 1) / lay.tile_height)
-                                : (lay.height + lay.rows_per_strip - 1) / lay.rows_per_strip;
-    const uint64_t row_bytes = ((uint64_t)unit_w * spp_row * lay.bits + 7) / 8;  // rows start on byte boundaries
+    const int unit_w = (int)g.unit_w, unit_h = (int)g.unit_h, planes = (int)g.planes, per_plane = (int)g.per_plane;
+    const uint64_t row_bytes = g.row_bytes;
     if (lay.bits < 8 && ((tiled && untile) || lay.predictor == 2)) {
         err = "layout: samples below 8 bits are neither untiled nor un-differenced here";
         return false;
     }
-    const uint64_t stride = ((uint64_t)unit_h * row_bytes + 255) & ~255ull;
+    const uint64_t stride = (g.unit_bytes + 255) & ~255ull;
     const bool decode = lay.compression > 1;
     if (!ensure<uint64_t>(soff, (size_t)ns * 2, err) || !ensure<int>(this->err, 4, err)) return false;
     if (decode && !ensure<uint8_t>(stage, stride * ns, err)) return false;
@@ -132,7 +128,7 @@ bool GpuEncoder::unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2h
         ua.h = lay.height;
         ua.row_bytes = row_bytes;
         ua.stride = stride;
-        ua.unit_bytes = tiled ? (uint64_t)unit_h * row_bytes : 0;
+        ua.unit_bytes = tiled ? g.unit_bytes : 0;
         ua.dst = (uint8_t *)stage.ptr;
         ua.only = nullptr;
         ua.lnk = nullptr;
@@ -154,9 +150,9 @@ bool GpuEncoder::unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2h
             if (!ensure<uint32_t>(inflnk, stride * ns, err)) return false;
             ua.lnk = (uint32_t *)inflnk.ptr;
             hipLaunchKernelGGL(k_inflate, dim3(ns), dim3(kInfLanes), 0, stream, ua);
-            const dim3 g((unsigned)((unit_h * row_bytes + kLinkChunk - 1) / kLinkChunk), (unsigned)ns);
+            const dim3 grid((unsigned)((g.unit_bytes + kLinkChunk - 1) / kLinkChunk), (unsigned)ns);
             for (int r = 0; r <= kLinkDoublings; r++)
-                hipLaunchKernelGGL(k_inflate_links, g, dim3(256), 0, stream, ua, r == kLinkDoublings ? 1 : 0);
+                hipLaunchKernelGGL(k_inflate_links, grid, dim3(256), 0, stream, ua, r == kLinkDoublings ? 1 : 0);
         }
         else hipLaunchKernelGGL(k_unpackbits, dim3(ns), dim3(64), 0, stream, ua);
         HIPCHECK(hipGetLastError());
@@ -179,7 +175,7 @@ bool GpuEncoder::unpack_strips(const void *d_src, const jp2hip_layout &lay, jp2h
         if (!ensure<uint8_t>(untiled, plane_bytes * planes, err)) return false;
         hipLaunchKernelGGL(k_untile, dim3((lay.width + 255) / 256, lay.height, planes), dim3(256), 0, stream,
                            (const uint8_t *)res, decode ? nullptr : (const uint64_t *)soff.ptr, stride, lay.width,
-                           lay.height, lay.tile_width, lay.tile_height, across, per_plane, px_bytes,
+                           lay.height, lay.tile_width, lay.tile_height, (int)g.across, per_plane, px_bytes,
                            (uint8_t *)untiled.ptr);
         HIPCHECK(hipGetLastError());
         for (int p = 0; p < planes; p++) out_offs[p] = (uint64_t)p * plane_bytes;
