@@ -138,10 +138,23 @@ def lzw_encode(data: bytes, clear_every: int | None = None, clear_when_full: boo
     return bytes(out)
 
 
+def predict2(blk: np.ndarray) -> np.ndarray:
+    """Predictor 2 as a writer applies it to (rows, width, samples) of
+    unsigned samples: every sample less the same component of the pixel to
+    its left, modulo 2^bits (unsigned numpy arithmetic wraps); the first
+    pixel of a row stays."""
+    assert blk.ndim == 3 and blk.dtype in (np.uint8, np.uint16)
+    out = blk.copy()
+    out[:, 1:] = blk[:, 1:] - blk[:, :-1]
+    return out
+
+
 def tiff_bytes(img: np.ndarray, rows_per_strip=64, planar=False, big_endian=False,
-               alpha=None, strip_codec=None, compression=1) -> bytes:
+               alpha=None, strip_codec=None, compression=1, predictor=1) -> bytes:
     """Baseline TIFF (strips), 8/16-bit, 1-4 samples; uncompressed, or each
-    strip passed through `strip_codec` (then tagged `compression`)."""
+    strip passed through `strip_codec` (then tagged `compression`).
+    predictor=2: rows differenced (predict2) before the bytes are laid out in
+    the file's byte order, and tagged Predictor 2."""
     if img.ndim == 2:
         img = img[..., None]
     h, w, nc = img.shape
@@ -154,10 +167,12 @@ def tiff_bytes(img: np.ndarray, rows_per_strip=64, planar=False, big_endian=Fals
     for pl in planes:
         for s in range(nstrip):
             blk = np.ascontiguousarray(pl[s * rps:(s + 1) * rps])
+            if predictor == 2:
+                blk = predict2(blk.reshape(blk.shape[0], w, -1))
             strips.append(blk.astype(blk.dtype.newbyteorder(e)).tobytes())
     if strip_codec is not None:
         strips = [strip_codec(x) for x in strips]
-    ntags = 11 + (1 if nc in (2, 4) else 0)
+    ntags = 11 + (1 if nc in (2, 4) else 0) + (1 if predictor != 1 else 0)
     ifd_off = 8
     ifd_size = 2 + 12 * ntags + 4
     extra = bytearray()
@@ -211,6 +226,8 @@ def tiff_bytes(img: np.ndarray, rows_per_strip=64, planar=False, big_endian=Fals
     tag(278, 4, 1, rps)
     tag(279, 4, nst, len(strips[0]) if nst == 1 else sbc_off, inline=(nst == 1))
     tag(284, 3, 1, 2 if planar else 1)
+    if predictor != 1:
+        tag(317, 3, 1, predictor)
     if nc in (2, 4):
         tag(338, 3, 1, 2 if alpha is None else alpha)
     tag(339, 3, 1, 1)
@@ -489,9 +506,11 @@ def tiff_bytes_compressed(img: np.ndarray, compression: str, predictor: bool = F
     return data
 
 
-def bigtiff_bytes(img: np.ndarray, rows_per_strip=64, big_endian=False, strip_codec=None, compression=1) -> bytes:
+def bigtiff_bytes(img: np.ndarray, rows_per_strip=64, big_endian=False, strip_codec=None, compression=1,
+                  predictor=1) -> bytes:
     """Chunky BigTIFF (version 43, LONG8 strip offsets / counts); uncompressed,
-    or each strip passed through `strip_codec` (then tagged `compression`)."""
+    or each strip passed through `strip_codec` (then tagged `compression`);
+    predictor=2 as in tiff_bytes."""
     if img.ndim == 2:
         img = img[..., None]
     h, w, nc = img.shape
@@ -500,10 +519,12 @@ def bigtiff_bytes(img: np.ndarray, rows_per_strip=64, big_endian=False, strip_co
     rps = min(rows_per_strip, h)
     nst = (h + rps - 1) // rps
     strips = [np.ascontiguousarray(img[s * rps:(s + 1) * rps]) for s in range(nst)]
+    if predictor == 2:
+        strips = [predict2(b) for b in strips]
     strips = [b.astype(b.dtype.newbyteorder(e)).tobytes() for b in strips]
     if strip_codec is not None:
         strips = [strip_codec(x) for x in strips]
-    ntags = 10
+    ntags = 10 + (1 if predictor != 1 else 0)
     ifd_off = 16
     arr_off = ifd_off + 8 + 20 * ntags + 8
     so_off, sbc_off = arr_off, arr_off + 8 * nst
@@ -522,6 +543,8 @@ def bigtiff_bytes(img: np.ndarray, rows_per_strip=64, big_endian=False, strip_co
             ent(262, 3, 1, [2 if nc >= 3 else 1]),
             ent(273, 16, nst, [offs[0]] if nst == 1 else [so_off]), ent(277, 3, 1, [nc]), ent(278, 4, 1, [rps]),
             ent(279, 16, nst, [len(strips[0])] if nst == 1 else [sbc_off]), ent(284, 3, 1, [1])]
+    if predictor != 1:
+        tags.append(ent(317, 3, 1, [predictor]))
     hdr = (b"MM" if big_endian else b"II") + struct.pack(e + "HHHQ", 43, 8, 0, ifd_off)
     ifd = struct.pack(e + "Q", ntags) + b"".join(tags) + struct.pack(e + "Q", 0)
     arrays = struct.pack(e + "Q" * nst, *offs) + struct.pack(e + "Q" * nst, *[len(s) for s in strips])
@@ -529,7 +552,8 @@ def bigtiff_bytes(img: np.ndarray, rows_per_strip=64, big_endian=False, strip_co
 
 
 def packbits_encode(raw: bytes) -> bytes:
-    """PackBits with literal runs only (valid, if not small)."""
+    """PackBits with literal runs only (valid, if not small).  Replicate runs,
+    no-ops and row-wise packing come from ingest_stream_cases.packbits_runs."""
     out = bytearray()
     for i in range(0, len(raw), 128):
         chunk = raw[i:i + 128]
@@ -539,11 +563,14 @@ def packbits_encode(raw: bytes) -> bytes:
 
 
 def tiled_tiff_bytes(img: np.ndarray, tile=(32, 48), planar=False, big_endian=False, packbits=False,
-                     deflate=False) -> bytes:
+                     deflate=False, codec=None, compression=None, predictor=1) -> bytes:
     """Classic tiled TIFF (TileWidth/TileLength/TileOffsets/TileByteCounts),
     uncompressed, PackBits or Deflate (zlib levels 0 / 1 / 9 in turn, so
     stored, fixed-Huffman and dynamic-Huffman blocks all occur); edge tiles
-    padded with zeros as TIFF requires."""
+    padded with zeros as TIFF requires.  codec=: every tile through that
+    strip codec (bytes -> bytes; LZW too) and tagged `compression`.
+    predictor=2: each row of a tile differenced after the padding
+    (predict2), then laid out in the file's byte order."""
     import zlib
     if img.ndim == 2:
         img = img[..., None]
@@ -560,13 +587,18 @@ def tiled_tiff_bytes(img: np.ndarray, tile=(32, 48), planar=False, big_endian=Fa
                 t = np.zeros((th, tw, pl.shape[2]), img.dtype)
                 part = pl[ty * th:(ty + 1) * th, tx * tw:(tx + 1) * tw]
                 t[:part.shape[0], :part.shape[1]] = part
+                if predictor == 2:
+                    t = predict2(t)
                 raw = t.astype(t.dtype.newbyteorder(e)).tobytes()
-                if deflate:
+                if codec is not None:
+                    tiles.append(codec(raw))
+                elif deflate:
                     tiles.append(zlib.compress(raw, (0, 1, 9)[len(tiles) % 3]))
                 else:
                     tiles.append(packbits_encode(raw) if packbits else raw)
+    assert (codec is None) == (compression is None) and not (codec and (packbits or deflate))
     nt = len(tiles)
-    ntags = 13
+    ntags = 13 + (1 if predictor != 1 else 0)
     ifd_off = 8
     extra_base = ifd_off + 2 + 12 * ntags + 4
     bps_off = extra_base
@@ -582,11 +614,17 @@ def tiled_tiff_bytes(img: np.ndarray, tile=(32, 48), planar=False, big_endian=Fa
         v = struct.pack(e + "HH", val, 0) if (typ == 3 and cnt == 1) else struct.pack(e + "I", val)
         return struct.pack(e + "HHI", tag, typ, cnt) + v
 
-    tags = [ent(256, 4, 1, w), ent(257, 4, 1, h), ent(258, 3, nc, bps_off) if nc > 1 else ent(258, 3, 1, bits),
-            ent(259, 3, 1, 8 if deflate else 32773 if packbits else 1), ent(262, 3, 1, 2 if nc >= 3 else 1), ent(277, 3, 1, nc),
+    bps = ent(258, 3, 1, bits) if nc == 1 else ent(258, 3, nc, bps_off)
+    if nc == 2:  # two SHORTs fit the entry: the values themselves, not an offset
+        bps = struct.pack(e + "HHIHH", 258, 3, 2, bits, bits)
+    tags = [ent(256, 4, 1, w), ent(257, 4, 1, h), bps,
+            ent(259, 3, 1, compression if codec else 8 if deflate else 32773 if packbits else 1),
+            ent(262, 3, 1, 2 if nc >= 3 else 1), ent(277, 3, 1, nc),
             ent(284, 3, 1, 2 if planar else 1), ent(322, 4, 1, tw), ent(323, 4, 1, th),
             ent(324, 4, nt, to_off if nt > 1 else offs[0]), ent(325, 4, nt, tbc_off if nt > 1 else len(tiles[0])),
             ent(339, 3, 1, 1), ent(338, 3, 1, 2) if nc in (2, 4) else ent(305, 2, 1, 0)]
+    if predictor != 1:
+        tags.append(ent(317, 3, 1, predictor))
     tags.sort(key=lambda t: struct.unpack(e + "H", t[:2])[0])
     hdr = (b"MM\0*" if big_endian else b"II*\0") + struct.pack(e + "I", ifd_off)
     ifd = struct.pack(e + "H", ntags) + b"".join(tags) + struct.pack(e + "I", 0)

@@ -70,17 +70,20 @@ def make_tiff(idx: np.ndarray, bits: int, photometric: int = BLACK_IS_ZERO, fill
               codec: str | None = None, tile: tuple[int, int] | None = None, bigtiff: bool = False) -> bytes:
     """The TIFF of `idx` (h x w values of `bits` bits).  tile = (width,
     height) in pixels: a tiled file (uncompressed, "packbits" or "deflate");
-    else strips, through `codec` (None, "lzw", "deflate", "packbits")."""
+    else strips, through `codec` (None, "lzw", "deflate", "packbits").
+    Either way `codec` may be a (bytes -> bytes, Compression value) pair."""
     h, w = idx.shape
     packed = pack_rows(idx, bits, fill_order or 1)
     if tile is not None:
         tw, th = tile
-        assert (tw * bits) % 8 == 0 and codec in (None, "packbits", "deflate") and not bigtiff
+        assert (tw * bits) % 8 == 0 and (codec in (None, "packbits", "deflate") or isinstance(codec, tuple))
+        assert not bigtiff
+        own = dict(codec=codec[0], compression=codec[1]) if isinstance(codec, tuple) else {}
         tif = im.tiled_tiff_bytes(packed, tile=(tw * bits // 8, th), big_endian=big_endian,
-                                  packbits=codec == "packbits", deflate=codec == "deflate")
+                                  packbits=codec == "packbits", deflate=codec == "deflate", **own)
         tif = im.tiff_set_tag(tif, 322, tw)
     else:
-        fn, code = CODECS[codec]
+        fn, code = codec if isinstance(codec, tuple) else CODECS[codec]
         writer = im.bigtiff_bytes if bigtiff else im.tiff_bytes
         tif = writer(packed, rows_per_strip=rows_per_strip, big_endian=big_endian, strip_codec=fn, compression=code)
     tif = im.tiff_set_tag(im.tiff_set_tag(im.tiff_set_tag(tif, 256, w), 258, bits), 262, photometric)
