@@ -1,0 +1,85 @@
+// context.h -- what the host sources behind the C ABI share (api.cpp,
+// encode.cpp, split_host.cpp): the context, its plan cache, the
+// end-of-encode memory policy and the error report.  Private to csrc.
+#pragma once
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "gpu_encoder.h"
+#include "jp2hip.h"
+#include "jp2hip_internal.h"
+#include "mem_policy.h"
+
+// The last geometry's plan, tier-2 tables and main-header length: a batch of
+// same-size images (the common case) builds them once (C2: ~5 ms of host
+// time per encode otherwise), and the device keeps their tables resident.
+struct PlanCache {
+    bool valid = false;
+    jp2hip_recipe rc;
+    int w = 0, h = 0, nc = 0, bits = 0;
+    jp2hip::Plan plan;
+    jp2hip::T2Tables tabs;
+    std::vector<uint8_t> mh0;
+};
+
+struct jp2hip_ctx {
+    std::mutex mu;
+    // whole tile-split encodes on this context, one at a time: each rank
+    // takes its member's `mu`, so two concurrent splits could otherwise hold
+    // one member each and wait for each other in an exchange
+    std::mutex split_mu;
+    jp2hip::GpuEncoder gpu;
+    jp2hip_config cfg;
+    int threads = 1;
+    PlanCache pc;
+    // tile-split members (jp2hip_split_peers): images of at least
+    // split_min_pixels are encoded by this context (rank 0) and these
+    // (ranks 1..), owned here
+    std::vector<jp2hip_ctx *> peers;
+    int64_t split_min_pixels = 0;
+    // device memory policy (jp2hip_set_memory_limits): 0 = default
+    int64_t mem_soft = 0;
+    size_t dev_total = 0;  // the device's memory (hipMemGetInfo at create)
+    std::vector<size_t> needs;  // what the last encodes asked for (the context's usual image)
+    int64_t reclaimed = 0;      // times another context took this one's idle buffers
+    ~jp2hip_ctx() {
+        for (jp2hip_ctx *p : peers) jp2hip_destroy(p);
+    }
+};
+
+// Sets this thread's jp2hip_last_error() text (api.cpp); returns -1.
+namespace jp2hip {
+int fail(const std::string &msg);
+}
+
+// Every encode ends here, success or not: a failed one drains the stream
+// first (no buffer is released while a kernel may still read it), then the
+// context's device-memory policy decides whether it keeps its buffers.
+//  - an explicit soft limit (jp2hip_set_memory_limits): release everything
+//    when the context holds more;
+//  - by default, relative to the context's usual image: release everything
+//    when it holds more than twice the median of what its last 8 encodes
+//    needed (plus 256 MiB) -- one C5-class master in a pool of C2 / C4 work
+//    is released right after it, while a steady run of large masters (C3
+//    every time) keeps its buffers instead of reallocating per image.
+// Memory pressure between contexts is handled where it arises: an
+// allocation that fails takes back what idle contexts of the device hold
+// (api.cpp reclaim_idle).  `ctx` stays null until the encode has begun
+// (encode.cpp begin_encode): a call refused before that leaves the context
+// as it was.
+struct EncodeEnd {
+    jp2hip_ctx *ctx = nullptr;
+    bool ok = false;
+    ~EncodeEnd() {
+        if (!ctx) return;
+        if (!ok) ctx->gpu.quiesce();
+        if (ok) jp2hip::record_need(ctx->needs, ctx->gpu.need_bytes());
+        const size_t limit = jp2hip::keep_limit(ctx->needs, ctx->mem_soft);  // (mem_policy.h)
+        if (ctx->gpu.device_bytes() > limit) {
+            ctx->gpu.quiesce();
+            ctx->gpu.trim(limit);
+        }
+    }
+};

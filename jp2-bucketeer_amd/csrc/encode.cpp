@@ -1,0 +1,483 @@
+// encode.cpp -- one encode on one context: the single-GPU encode (encode_core)
+// and one rank of a tile-split encode (encode_split_core).  They share how an
+// encode begins (begin), prepare_source, the rate target and first budget,
+// and how a rank's part of the file is written (finish_part).  Their rate
+// loops are different algorithms on purpose: the single encode runs the loop
+// on the device (GpuEncoder::rate_loop: one host wait, a retry when the
+// decision-stream pool was short; the benchmark measures this one), the split
+// encode iterates on the host over thresholds its ranks exchange, its pool
+// sized for the worst case (pool_worst: ranks cannot repeat an exchange).
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "context.h"
+#include "encode.h"
+#include "source_layout.h"
+
+namespace jp2hip {
+
+void default_recipe(jp2hip_recipe *r, int conversion) {
+    std::memset(r, 0, sizeof *r);
+    r->levels = 6;
+    r->layers = 6;
+    r->tile_w = r->tile_h = 512;
+    r->cblk_w_log2 = r->cblk_h_log2 = 6;
+    r->nprecincts = 3;
+    r->prec_w_log2[0] = r->prec_h_log2[0] = 8;
+    r->prec_w_log2[1] = r->prec_h_log2[1] = 8;
+    r->prec_w_log2[2] = r->prec_h_log2[2] = 7;
+    r->progression = 2;
+    r->sop = r->eph = r->plt = r->tparts_r = 1;
+    r->guard_bits = 1;
+    bool lossless = conversion == JP2HIP_LOSSLESS;
+    r->reversible = lossless ? 1 : 0;
+    r->mct = 1;
+    r->qstep = 1.0 / 256.0;
+    r->rate_bpp = lossless ? 0.0 : 3.0;
+    r->format = JP2HIP_FORMAT_JPX;
+    r->comment = 1;
+    r->slope_skip = 1;
+    r->flush_period = 1024;
+}
+
+// The caller's recipe (or the default for `conversion`) with its padding
+// bytes zeroed, so PlanCache's byte compare sees only the fields.
+jp2hip_recipe recipe_of(const jp2hip_recipe *recipe, int conversion) {
+    jp2hip_recipe rc;
+    std::memset(&rc, 0, sizeof rc);
+    if (recipe) rc = *recipe;
+    else default_recipe(&rc, conversion);
+    const size_t gap0 = offsetof(jp2hip_recipe, mct) + sizeof rc.mct, gap1 = offsetof(jp2hip_recipe, qstep);
+    if (gap1 > gap0) std::memset((char *)&rc + gap0, 0, gap1 - gap0);
+    static_assert(offsetof(jp2hip_recipe, flush_period) + sizeof(int32_t) == sizeof(jp2hip_recipe),
+                  "jp2hip_recipe: no tail padding");
+    return rc;
+}
+
+namespace {
+
+// A rate-driven encode's target (bytes): the floor(rate * W * H / 8) the
+// oracle's predict_and_code uses; slope prediction's is the same (0 = off).
+int64_t rate_target_of(const jp2hip_recipe &rc, int w, int h) {
+    return (int64_t)std::floor(rc.rate_bpp * (double)w * (double)h / 8.0);
+}
+int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h) {
+    return rc.slope_skip && rc.rate_bpp > 0.0 ? rate_target_of(rc, w, h) : 0;
+}
+// The rate loop's first budget: its header estimate (16 bytes per packet)
+// lands the usual encode under the target (C2: 8 985 521 of 9 000 000 bytes).
+int64_t first_budget_of(const Plan &P, int64_t target) { return target - 16 * P.npackets - 16 * P.ntileparts - 256; }
+
+// How both encodes begin: the checks (sp: a split's rank and group), the
+// recipe, what the source states about its pixels (into the file header, per
+// encode: a cached plan is shared by files that differ in it) and the
+// context's per-encode counters; `end` is armed last.
+int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conversion, const jp2hip_recipe *recipe,
+          const jp2hip_split *sp, jp2hip_recipe &rc, SourceMeta &meta, EncodeEnd &end) {
+    if (conversion != JP2HIP_LOSSY && conversion != JP2HIP_LOSSLESS)
+        return fail("conversion must be JP2HIP_LOSSY (0) or JP2HIP_LOSSLESS (1)");
+    const int world = sp ? sp->world : 1, rank = sp ? sp->rank : 0;
+    if (world < 1 || rank < 0 || rank >= world) return fail("split: bad rank / world");
+    if (world > 1 && !sp->allreduce_sum) return fail("split: world > 1 needs an allreduce_sum callback");
+    rc = recipe_of(recipe, conversion);
+    if (!lay || !d_src) return fail("null source or layout");
+    meta = source_meta(*lay);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
+    ctx->gpu.take_waits();     // count this encode's host waits (stats)
+    ctx->gpu.begin_encode();
+    end.ctx = ctx;
+    return 0;
+}
+
+// One rank's part of the file: the file and main headers (with_main: rank
+// 0), the tile-parts it coded (have), EOC (with_eoc: the last rank).  The
+// single encode is the one rank that has all three.
+struct FilePart {
+    const Plan &file, &coded;  // names the file (the plan / a split's full plan); was coded here (the plan / sub)
+    bool with_main, with_eoc, have;
+    size_t fh = 0, head = 0, bytes = 0;  // file header; through the main header; the whole part
+    void size(const SourceMeta &meta, size_t mh_bytes, int64_t part_bytes) {
+        fh = with_main ? file_header_bytes(file, meta) : 0;
+        head = with_main ? fh + mh_bytes : 0;
+        bytes = head + (size_t)(have ? part_bytes : 0) + (with_eoc ? 2 : 0);
+    }
+};
+
+// Writes part `fp` into `buf` (pinned, fp.bytes long; released here on
+// failure) and hands it to the caller with the encode's stats.  K: the final
+// selection's slope keys; tp_hdr, layer_bytes, cs_bytes: whole-image sums
+// (Kdu-Layer-Info, the file header's code-stream length); file_bytes: the
+// whole file.
+int finish_part(jp2hip_ctx *ctx, const FilePart &fp, const SourceMeta &meta, std::vector<uint64_t> K, int64_t tp_hdr,
+                const int64_t *layer_bytes, int64_t cs_bytes, const T2Summary &sum, uint8_t *buf, StageTimes &st,
+                uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start, double h2d_ms,
+                int64_t file_bytes, int iters) {
+    const Plan &P = fp.file;
+    std::string err;
+    if (fp.with_main) {
+        // Kdu-Layer-Info: the slope keys (lossless: the last layer takes
+        // every pass) and the code-stream bytes through each layer
+        const int L = P.rc.layers;
+        if (P.rc.rate_bpp <= 0.0) K[L - 1] = 0;
+        std::vector<int64_t> layer_end((size_t)L);
+        int64_t acc = (int64_t)(fp.head - fp.fh) + tp_hdr;
+        for (int l = 0; l < L; l++) layer_end[l] = acc += layer_bytes[l];
+        std::vector<uint8_t> mh;
+        main_header(P, mh, K.data(), layer_end.data());
+        write_file_header(P, meta, (uint64_t)cs_bytes, buf);
+        std::memcpy(buf + fp.fh, mh.data(), mh.size());
+    }
+    const bool prof = ctx->cfg.profile != 0;
+    if (fp.have && (!ctx->gpu.t2_emit(fp.coded, 0, (uint64_t)sum.part_bytes, buf + fp.head, prof, st, err) ||
+                    !ctx->gpu.collect_profile(st, err))) {
+        out_free(buf);
+        return fail(err);
+    }
+    if (fp.with_eoc) {
+        buf[fp.bytes - 2] = 0xFF;
+        buf[fp.bytes - 1] = 0xD9;
+    }
+    *out = buf;
+    *out_len = fp.bytes;
+    if (!stats) return 0;
+    std::memset(stats, 0, sizeof *stats);
+    stats->total_ms = now_ms() - t_start;
+    stats->h2d_ms = h2d_ms;
+    stats->ingest_ms = st.ingest;
+    stats->dwt_ms = st.dwt;
+    stats->quant_ms = st.quant;
+    stats->t1_ms = st.t1_cm + st.t1_mq;
+    stats->t1_cm_ms = st.t1_cm;
+    stats->t1_mq_ms = st.t1_mq;
+    stats->pcrd_ms = st.pcrd;
+    stats->d2h_ms = st.d2h;
+    stats->t2_ms = st.t2;
+    stats->codeblocks = (int64_t)fp.coded.blocks.size();
+    stats->t1_bytes = sum.t1_bytes;
+    stats->coded_passes = sum.coded_passes;
+    stats->out_bytes = file_bytes;
+    stats->rate_iterations = iters;
+    stats->host_waits = ctx->gpu.take_waits();
+    stats->mq_decisions = sum.decisions;
+    stats->stream_need_bytes = sum.stream_need;
+    stats->stream_pool_bytes = (int64_t)ctx->gpu.stream_pool_bytes();
+    stats->pool_grows = ctx->gpu.take_pool_grows();
+    return 0;
+}
+
+}  // namespace
+
+// The whole encode with the source already in device memory.  On success
+// *out is the complete file in a pinned buffer from this library's pool
+// (out_alloc; released with jp2hip_free).  Everything up to the code-stream
+// bytes runs on the GPU (tier-2 included, t2_device.hip); the host picks the
+// rate-control budgets from one small summary per pass and writes the file
+// and main headers.
+int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
+                const jp2hip_recipe *recipe, uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start,
+                double h2d_ms) {
+    jp2hip_recipe rc;
+    SourceMeta meta;
+    EncodeEnd end;
+    if (begin(ctx, d_src, lay, conversion, recipe, nullptr, rc, meta, end)) return -1;
+    std::string err;
+    jp2hip_layout ulay;
+    std::vector<uint64_t> uoffs;
+    UnitGrid grid;
+    if (!unit_grid(*lay, grid, err) || !prepare_source(ctx, grid, d_src, src_len, lay, 0, lay->height, ulay, uoffs, err))
+        return fail(err);
+    PlanCache &pc = ctx->pc;
+    if (!pc.valid || pc.w != lay->width || pc.h != lay->height || pc.nc != lay->components || pc.bits != lay->bits ||
+        std::memcmp(&pc.rc, &rc, sizeof rc) != 0) {
+        pc.valid = false;
+        if (!build_plan(pc.plan, rc, lay->width, lay->height, lay->components, lay->bits, err)) return fail(err);
+        t2_tables(pc.plan, 0, pc.plan.ntx * pc.plan.nty, 0, pc.tabs);
+        main_header(pc.plan, pc.mh0, nullptr, nullptr);
+        pc.rc = rc;
+        pc.w = lay->width; pc.h = lay->height; pc.nc = lay->components; pc.bits = lay->bits;
+        pc.valid = true;
+    }
+    const Plan &plan = pc.plan;
+    const bool prof = ctx->cfg.profile != 0;
+    StageTimes st;
+    int64_t skip_target = skip_target_of(rc, plan.w, plan.h);
+    // tier-2 tables first: every host->device copy of the encode is issued
+    // while the stream is idle (a copy queued behind kernels holds up the
+    // copy engine for the other contexts)
+    if (!ctx->gpu.t2_load(plan, pc.tabs, err)) return fail(err);
+    if (!ctx->gpu.run_front(d_src, *lay, plan, prof, st, err, skip_target)) return fail(err);
+    const size_t mh_bytes = pc.mh0.size();
+    T2Summary sum;
+    std::memset(&sum, 0, sizeof sum);
+    int iters = 0;
+    int64_t cs_bytes = 0;
+    if (rc.rate_bpp <= 0.0) {
+        // lossless: per -flush_period stripe, layer l keeps the passes whose
+        // slopes clear lossless_layer_frac(l) of the stripe's tier-1 bytes
+        for (int grow = 0;; grow++) {
+            if (!ctx->gpu.select_lossless(plan, err) || !ctx->gpu.t2_size(plan, true, prof, st, sum, err))
+                return fail(err);
+            if ((sum.err & kErrSlotPool) && grow < 2) {
+                // the decision-stream pool was short: again with the size
+                // this encode needed (GpuEncoder::run_front)
+                if (!ctx->gpu.pool_grow(err) || !ctx->gpu.run_front(d_src, *lay, plan, prof, st, err, skip_target))
+                    return fail(err);
+                continue;
+            }
+            break;
+        }
+        if (sum.err) return fail("tier-1 output capacity exceeded");
+        iters = 1;
+        cs_bytes = (int64_t)mh_bytes + sum.part_bytes + 2;
+    } else {
+        // the rate loop runs on the device (GpuEncoder::rate_loop): one
+        // iteration per host wait, what the usual encode needs (its first
+        // budget lands it under the target); an encode whose headers are
+        // heavier takes a second wait for its next iterations
+        RateState init;
+        std::memset(&init, 0, sizeof init);
+        init.target = rate_target_of(rc, plan.w, plan.h);
+        init.budget = first_budget_of(plan, init.target);
+        init.fixed = (int64_t)mh_bytes + 2;
+        init.skip_target = skip_target;
+        RateState rs;
+        bool restart = true;
+        for (int grow = 0;;) {
+            if (!ctx->gpu.rate_loop(plan, init, restart, restart ? 1 : 2, prof, st, rs, sum, err)) return fail(err);
+            restart = false;
+            if ((sum.err & kErrSlotPool) && grow++ < 2) {
+                // the decision-stream pool was short: again with the size
+                // this encode needed (GpuEncoder::run_front)
+                if (!ctx->gpu.pool_grow(err) ||
+                    !ctx->gpu.run_front(d_src, *lay, plan, prof, st, err, init.skip_target))
+                    return fail(err);
+                restart = true;
+                continue;
+            }
+            if (sum.err) return fail("tier-1 output capacity exceeded");
+            if (rs.safety) {
+                // slope prediction's safety net (oracle predict_and_code):
+                // planes were skipped, yet every coded byte fits -> code all
+                init.skip_target = 0;
+                if (!ctx->gpu.run_front(d_src, *lay, plan, prof, st, err, 0)) return fail(err);
+                restart = true;
+                continue;
+            }
+            if (rs.halt) break;
+        }
+        iters = rs.iters;
+        cs_bytes = rs.cs_bytes;  // (= init.fixed + sum.part_bytes: device_common.h rate_step)
+    }
+    FilePart fp{plan, plan, true, true, true};
+    fp.size(meta, mh_bytes, sum.part_bytes);
+    uint8_t *buf = out_alloc(fp.bytes);
+    if (!buf) return fail("out of (pinned) host memory");
+    if (finish_part(ctx, fp, meta, std::vector<uint64_t>(sum.kc, sum.kc + rc.layers), sum.tp_hdr_bytes,
+                    sum.layer_bytes, cs_bytes, sum, buf, st, out, out_len, stats, t_start, h2d_ms, (int64_t)fp.bytes,
+                    iters))
+        return -1;
+    end.ok = true;
+    return 0;
+}
+
+// Tile-split encode (jp2hip.h, jp2hip_encode_device_split; split.cpp has the
+// exchange rule).  Rank `rank` runs the device pipeline -- tier-2 included --
+// on its band of tile rows only; budgets, thresholds and tier-2 sizes are
+// agreed through sp->allreduce_sum so the parts concatenate to the
+// single-GPU file.
+int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
+                      const jp2hip_recipe *recipe, const jp2hip_split *sp, uint8_t **out, size_t *out_len,
+                      uint64_t *file_offset, uint64_t *file_len, jp2hip_stats *stats, double t_start) {
+    jp2hip_recipe rc;
+    SourceMeta meta;
+    EncodeEnd end;
+    if (begin(ctx, d_src, lay, conversion, recipe, sp, rc, meta, end)) return -1;
+    const int world = sp ? sp->world : 1, rank = sp ? sp->rank : 0;
+    std::string err;
+    auto allreduce = [&](int64_t *v, int n) {
+        return world <= 1 || sp->allreduce_sum(sp->user, v, (int32_t)n) == 0;
+    };
+    // An exchange that carries a failure flag in v[flag], so that a rank
+    // which failed still joins it and the others learn of it: `ok` goes in
+    // and comes back false if any rank failed (err: this rank's own text when
+    // it failed first-hand).  Returns false when the exchange itself failed:
+    // no later one can work, the caller returns.
+    auto exchange = [&](std::vector<int64_t> &v, size_t flag, bool &ok) {
+        v[flag] = ok ? 0 : 1;
+        if (!allreduce(v.data(), (int)v.size())) {
+            err = "split: all-reduce failed";
+            return false;
+        }
+        if (ok && v[flag]) {
+            ok = false;
+            err = "split: another rank failed";
+        }
+        return true;
+    };
+    Plan full;
+    UnitGrid grid;  // (the same on every rank: a layout it refuses fails them all here)
+    if (!unit_grid(*lay, grid, err)) return fail(err);
+    int enc_nc, enc_bits;  // the plan sees what the code-stream carries
+    encoded_format(*lay, enc_nc, enc_bits);
+    if (!build_plan(full, rc, lay->width, lay->height, enc_nc, enc_bits, err)) return fail(err);
+    int tr0, tr1;
+    split_tile_rows(full.nty, rc.tile_h, full.h, rc.flush_period, rank, world, tr0, tr1);
+    Plan sub;
+    make_subplan(full, tr0, tr1, sub);
+    const bool have = sub.ntc > 0;
+    // only this rank's rows are read, so only their strips (or tiles) must be
+    // in d_src; compressed / tiled units of the band are decoded here (a rank
+    // that fails here still joins every exchange below)
+    jp2hip_layout ulay;
+    std::vector<uint64_t> uoffs;
+    bool ok = !have || prepare_source(ctx, grid, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err);
+    const bool prof = ctx->cfg.profile != 0;
+    StageTimes st;
+    std::vector<uint64_t> keys;
+    std::vector<int64_t> cum;
+    // slope prediction over the whole image: the plane histogram is summed
+    // over ranks (one all-reduce of kSlopeBins + 1 int64, the last a failure
+    // flag, so a rank that failed earlier still joins the exchange)
+    int64_t skip_target = skip_target_of(rc, full.w, full.h);
+    bool hist_done = false;
+    GpuEncoder::HistReduce reduce = [&](std::vector<int64_t> &h) {
+        hist_done = true;
+        std::vector<int64_t> v(h.size() + 1, 0);
+        std::copy(h.begin(), h.end(), v.begin());
+        bool all = true;
+        if (!exchange(v, h.size(), all) || !all) return false;
+        std::copy(v.begin(), v.end() - 1, h.begin());
+        return true;
+    };
+    T2Tables tabs;  // loaded before the front (host->device copies on an idle stream)
+    const int tile0 = sub.tile0, tile1 = sub.tile0 + full.ntx * (tr1 - tr0);
+    if (ok && have) {
+        t2_tables(full, tile0, tile1, sub.block0, tabs);
+        ok = ctx->gpu.t2_load(sub, tabs, err);
+    }
+    ok = ok && (!have || ctx->gpu.run_front(d_src, *lay, sub, prof, st, err, skip_target, &reduce, true));
+    if (skip_target > 0 && !hist_done) {  // no blocks here, or failed before the exchange
+        std::vector<int64_t> v((size_t)kSlopeBins + 1, 0);
+        if (!exchange(v, (size_t)kSlopeBins, ok)) return fail(err);
+    }
+    const int L = rc.layers;
+    std::vector<int64_t> budgets((size_t)L, 0);
+    std::vector<uint64_t> K((size_t)L);
+    int iters = 0;
+    int64_t cs_bytes = 0;
+    T2Summary sum;
+    std::memset(&sum, 0, sizeof sum);
+    int64_t g_tp_hdr = 0;                          // whole-image sums of the last pass
+    std::vector<int64_t> g_layer((size_t)L, 0);    // (Kdu-Layer-Info)
+    std::vector<uint8_t> mh;
+    main_header(full, mh, nullptr, nullptr);
+    // One selection (rate-driven: at the thresholds of `budgets`) and tier-2
+    // sizing pass, its sums exchanged: [0] part bytes, [1] failure flag, [2]
+    // tile-part header bytes, [3..] packet bytes per layer (Kdu-Layer-Info),
+    // then, lossless, L slope keys per rank.  False on failure (err).
+    auto round = [&](bool lossless) -> bool {
+        if (!lossless && jp2hip_split_thresholds(keys.data(), cum.data(), (int64_t)keys.size(), budgets.data(), L, sp,
+                                                 K.data()) != 0) {
+            err = "split: threshold exchange failed";
+            return false;
+        }
+        bool rok = ok;
+        if (rok && have)
+            rok = (lossless ? ctx->gpu.select_lossless(sub, err) : ctx->gpu.select_keys(sub, K, err)) &&
+                  ctx->gpu.t2_size(sub, lossless, prof, st, sum, err);
+        if (rok && have && sum.err) {
+            rok = false;
+            err = "tier-1 output capacity exceeded";
+        }
+        std::vector<int64_t> v((size_t)L + 3 + (lossless ? (size_t)world * L : 0), 0);
+        if (rok && have) {
+            v[0] = sum.part_bytes;
+            v[2] = sum.tp_hdr_bytes;
+            for (int l = 0; l < L; l++) {
+                v[3 + l] = sum.layer_bytes[l];
+                if (lossless) v[3 + L + (size_t)rank * L + l] = (int64_t)sum.kc[l];  // (positive doubles: < 2^63)
+            }
+        }
+        if (!exchange(v, 1, rok) || !rok) return false;
+        cs_bytes = (int64_t)mh.size() + 2 + v[0];
+        g_tp_hdr = v[2];
+        g_layer.assign(v.begin() + 3, v.begin() + 3 + L);
+        iters++;
+        for (int l = 0; lossless && l < L; l++) {  // a layer's key: the largest over the ranks' stripes
+            K[l] = 0;
+            for (int r = 0; r < world; r++) K[l] = std::max(K[l], (uint64_t)v[3 + L + (size_t)r * L + l]);
+        }
+        return true;
+    };
+    for (int attempt = 0; attempt < 2; attempt++) {
+        if (attempt == 1) {  // the prediction's safety net, decided globally (below)
+            keys.clear();
+            cum.clear();
+            ok = !have || ctx->gpu.run_front(d_src, *lay, sub, prof, st, err, 0, nullptr, true);
+            skip_target = 0;
+            iters = 0;
+        }
+        if (rc.rate_bpp <= 0.0) {
+            // lossless: every -flush_period stripe's layers come from its own
+            // tier-1 bytes (the plan's rate-control groups; a rank holds
+            // whole stripes), so the selection needs no exchange -- only the
+            // part sizes, the Kdu-Layer-Info bytes and the slope keys are shared
+            if (!round(true)) return fail(err);
+            break;
+        }
+        ok = ok && (!have || ctx->gpu.segments(sub, keys, cum, err));
+        std::vector<int64_t> flag(1);
+        if (!exchange(flag, 0, ok) || !ok) return fail(err);
+        const int64_t target = rate_target_of(rc, full.w, full.h);
+        int64_t budget = first_budget_of(full, target);
+        bool rerun = false;
+        for (int it = 0; it < 8; it++) {
+            if (budget < 0) budget = 0;
+            for (int l = 0; l < L; l++) budgets[l] = budget >> (L - 1 - l);
+            if (!round(false)) return fail(err);
+            if (it == 0 && skip_target > 0) {
+                int64_t v[2] = {have ? sum.t1_bytes : 0, have ? sum.skipped : 0};
+                if (!allreduce(v, 2)) return fail("split: all-reduce failed");
+                if (v[1] && v[0] < skip_target) { rerun = true; break; }
+            }
+            if (cs_bytes <= target) break;
+            // exponential back-off + 1/16 of the overshoot + 64 B (device_common.h rate_step)
+            budget -= ((cs_bytes - target) << it) + ((cs_bytes - target) >> 4) + 64;
+        }
+        if (!rerun) break;
+    }
+    // this rank's part of the file.  Everything its emission allocates is
+    // allocated before the ranks agree on the part sizes, so a rank that
+    // cannot fails with the others (the failure slot sizes[world]); a HIP
+    // error in the emission itself, after the exchange, fails this rank
+    // alone: the caller treats any rank's failure as the encode's (jp2hip.h)
+    FilePart fp{full, sub, rank == 0, rank == world - 1, have};
+    fp.size(meta, mh.size(), sum.part_bytes);
+    uint8_t *buf = out_alloc(fp.bytes);
+    bool ready = buf != nullptr;
+    if (!ready) err = "out of (pinned) host memory";
+    if (ready && have) ready = ctx->gpu.t2_reserve(sum.part_bytes, err);
+    std::vector<int64_t> sizes((size_t)world + 1, 0);
+    sizes[rank] = (int64_t)fp.bytes;
+    if (!exchange(sizes, (size_t)world, ready) || !ready) {
+        out_free(buf);
+        return fail(err);
+    }
+    uint64_t off = 0, flen = 0;
+    for (int r = 0; r < world; r++) {
+        if (r < rank) off += (uint64_t)sizes[r];
+        flen += (uint64_t)sizes[r];
+    }
+    if (finish_part(ctx, fp, meta, K, g_tp_hdr, g_layer.data(), cs_bytes, sum, buf, st, out, out_len, stats, t_start,
+                    0.0, (int64_t)flen, iters))
+        return -1;
+    if (file_offset) *file_offset = off;
+    if (file_len) *file_len = flen;
+    end.ok = true;
+    return 0;
+}
+
+}  // namespace jp2hip

@@ -1,0 +1,38 @@
+// encode.h -- what the host sources behind the C ABI call in each other.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "jp2hip.h"
+
+struct jp2hip_ctx;
+
+namespace jp2hip {
+struct UnitGrid;
+
+// api.cpp: the pinned output pool (pinned_pool.h) and the clock of the stats
+uint8_t *out_alloc(size_t n);
+void out_free(void *p);
+double now_ms();
+// prepare_source.cpp
+bool prepare_source(jp2hip_ctx *ctx, const UnitGrid &g, const void *&d_src, size_t src_len, const jp2hip_layout *&lay,
+                    int row0, int row1, jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err);
+// encode.cpp (the caller holds ctx->mu)
+void default_recipe(jp2hip_recipe *r, int conversion);
+jp2hip_recipe recipe_of(const jp2hip_recipe *recipe, int conversion);
+int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
+                const jp2hip_recipe *recipe, uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start,
+                double h2d_ms);
+int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
+                      const jp2hip_recipe *recipe, const jp2hip_split *sp, uint8_t **out, size_t *out_len,
+                      uint64_t *file_offset, uint64_t *file_len, jp2hip_stats *stats, double t_start);
+// split_host.cpp
+bool wants_split(const jp2hip_ctx *ctx, const jp2hip_layout &lay);
+int encode_split_host(jp2hip_ctx *ctx, const uint8_t *file, size_t flen, const jp2hip_layout &lay, int conversion,
+                      const jp2hip_recipe *recipe, int fd, uint8_t **out, size_t *out_len, jp2hip_stats *stats,
+                      double t0);
+
+}  // namespace jp2hip

@@ -89,7 +89,7 @@ class GpuEncoder {
         return n;
     }
     // called when hipMalloc fails: frees what other, idle contexts of the
-    // device hold (api.cpp); true if anything was released
+    // device hold (api.cpp reclaim_idle); true if anything was released
     std::function<bool()> reclaim;
     // waits for the stream, ignoring its errors (failure paths: no buffer is
     // released or reused while kernels may still read it)
@@ -105,7 +105,7 @@ class GpuEncoder {
     // (sources that expand_samples reads next, which untiles itself): decoded
     // tiles stay tiles, one per entry of out_offs.  `g` is lay's grid
     // (source_layout.h unit_grid): lay's table holds exactly the units of
-    // its height, each checked against the source (api.cpp prepare_source)
+    // its height, each checked against the source (prepare_source.cpp)
     bool unpack_strips(const void *d_src, const jp2hip_layout &lay, const UnitGrid &g, jp2hip_layout &out,
                        std::vector<uint64_t> &out_offs, const void **d_out, std::string &err, bool untile = true);
 

@@ -1,6 +1,6 @@
 // jp2hip_internal.h -- host-side model of one encode (geometry, quantiser,
 // code-block table) shared by the HIP launch code (the .hip stage files), tier-2
-// (t2.cpp) and the C ABI (api.cpp).  Where the source's samples lie (TIFF
+// (t2.cpp) and the encodes behind the C ABI (encode.cpp).  Where the source's samples lie (TIFF
 // parser, strip / tile grid, band bounds) is source_layout.h, not here.
 #pragma once
 

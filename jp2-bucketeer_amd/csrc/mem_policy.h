@@ -1,4 +1,4 @@
-// A context's device-memory decisions, as pure functions (api.cpp EncodeEnd
+// A context's device-memory decisions, as pure functions (context.h EncodeEnd
 // uses them; tests/host/test_mem_policy.cpp checks them on the CPU).
 #pragma once
 

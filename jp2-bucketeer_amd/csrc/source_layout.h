@@ -1,7 +1,7 @@
 // source_layout.h -- which bytes of a source buffer hold the image: the
 // baseline TIFF parser, the pixel-format rules, and the one description of a
 // layout's unit grid (strips or tiles) and of the units a band of rows reads.
-// Every path that hands a jp2hip_layout to a kernel (api.cpp prepare_source,
+// Every path that hands a jp2hip_layout to a kernel (prepare_source.cpp,
 // the encode_file split path, GpuEncoder::unpack_strips / expand_samples)
 // takes its geometry and its bounds checks from here.  Host-only: jp2hip.h
 // and the standard library, so the CPU suite builds it under ASan / UBSan

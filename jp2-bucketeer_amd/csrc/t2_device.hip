@@ -1358,7 +1358,7 @@ bool GpuEncoder::t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, u
         hipLaunchKernelGGL(k_t2_code<true>, dim3((t2_nprec + 63) / 64), dim3(64), 0, stream, a);
     if (nb) hipLaunchKernelGGL(k_t2_copy, dim3((nb + 3) / 4), dim3(256), 0, stream, a, nb, (const uint8_t *)t1out.ptr);
     HIPCHECK(hipGetLastError());
-    // host_dst is pinned (api.cpp out_alloc)
+    // host_dst is pinned (api.cpp out_alloc: pinned_pool.h)
 #if defined(JP2HIP_DIAG_NO_D2H)  // diagnostic builds only: the code-stream never leaves the GPU (output invalid)
     HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
     if (!host_wait(err)) return false;

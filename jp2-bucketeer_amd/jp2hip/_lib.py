@@ -123,10 +123,10 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            # batch path (csrc/batch.cpp; bound in jp2hip.batch)
            "jp2hip_batch_create", "jp2hip_batch_submit", "jp2hip_batch_wait", "jp2hip_batch_pending",
            "jp2hip_batch_destroy",
-           # tile-split path (csrc/split.cpp + api.cpp; bound in jp2hip.split)
+           # tile-split path (csrc/split.cpp, encode.cpp, split_host.cpp; bound in jp2hip.split)
            "jp2hip_split_rows", "jp2hip_encode_device_split", "jp2hip_split_thresholds",
            "jp2hip_split_peers", "jp2hip_tiff_pixels", "jp2hip_env_check",
-           # device-memory policy (api.cpp)
+           # device-memory policy (api.cpp; csrc/context.h EncodeEnd)
            "jp2hip_device_bytes", "jp2hip_set_memory_limits", "jp2hip_device_memory", "jp2hip_dma_engines")
 
 

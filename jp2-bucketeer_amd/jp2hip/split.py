@@ -155,7 +155,7 @@ def band_strips(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
     touch only the rows of their band).  Compressed strips and tiles are
     packed whole, with their byte counts (the ``offsets`` array then holds
     the offsets followed by the counts, as jp2hip.tiff_layout returns them);
-    the encoder decodes only the band's units (api.cpp prepare_source, over
+    the encoder decodes only the band's units (csrc/prepare_source.cpp, over
     the band walk of csrc/source_layout.cpp)."""
     if layout.compression > 1 or layout.tile_width > 0:
         return _band_units(tif, layout, offsets, row0, row1)

@@ -26,7 +26,7 @@ def test_dma_to_host_has_no_unbounded_wait():
 
 
 def test_memory_policy_on_cpu(tmp_path):
-    """The release-after-encode rule (csrc/mem_policy.h, used by api.cpp's
+    """The release-after-encode rule (csrc/mem_policy.h, used by context.h's
     EncodeEnd): keep a steady large footprint, release after an outsized
     image, an explicit soft limit wins."""
     exe = tmp_path / "test_mem_policy"

@@ -309,6 +309,63 @@ def test_split_slope_prediction_is_global(encoder):
         assert got == single, world
 
 
+class _RecordingGroup(js.ThreadGroup):
+    """A ThreadGroup that notes the length of every all-reduce, per rank."""
+
+    made = []
+
+    def __init__(self, world):
+        super().__init__(world)
+        self.calls = [[] for _ in range(world)]
+        _RecordingGroup.made.append(self)
+
+    def _allreduce(self, rank, values):
+        self.calls[rank].append(len(values))
+        super()._allreduce(rank, values)
+
+
+@pytest.mark.gpu
+def test_split_exchange_protocol(encoder, monkeypatch):
+    """The exchanges of one tile-split encode, by length, in order (csrc/encode.cpp
+    encode_split_core, csrc/split.cpp): every rank of a group -- in-process or
+    torch.distributed -- must make the same calls, so their number, order and
+    lengths are part of the interface.  1300x700 RGB8, tile 256, world 2."""
+    slope_bins = 1024  # csrc/jp2hip_internal.h kSlopeBins
+    world = 2
+    img = im.synth_rgb8(1300, 700, seed=2000)
+    tif = im.tiff_bytes(img)
+    monkeypatch.setattr(js, "ThreadGroup", _RecordingGroup)
+    seqs = {}
+    for conv in (jp2hip.LOSSLESS, jp2hip.LOSSY):
+        rc = jp2hip.recipe(conv, levels=6, tile_w=256, tile_h=256)
+        _RecordingGroup.made.clear()
+        _encode_world(tif, conv, rc, world)
+        (g,) = _RecordingGroup.made
+        assert all(c == g.calls[0] for c in g.calls), g.calls
+        seqs[conv] = (g.calls[0], rc.layers)
+    seq, L = seqs[jp2hip.LOSSLESS]
+    # part bytes, failure flag, tile-part header bytes, L layer sums, L keys
+    # per rank; then the part sizes and their failure flag
+    assert seq == [3 + L + world * L, world + 1]
+    seq, L = seqs[jp2hip.LOSSY]
+    assert L not in (1, 2, world + 1, slope_bins + 1)  # the lengths below tell the steps apart
+    # the plane histogram (+ flag), the segments flag, ..., the part sizes (+ flag)
+    assert seq[0] == slope_bins + 1 and seq[1] == 1 and seq[-1] == world + 1, seq
+    body, i, iterations = seq[2:-1], 0, 0
+    while i < len(body):
+        steps = 0
+        while i < len(body) and body[i] == L:  # the threshold bisection
+            steps, i = steps + 1, i + 1
+        assert steps <= 64, seq
+        assert i < len(body) and body[i] == L + 3, seq  # the sizing pass
+        i += 1
+        if iterations == 0:  # slope prediction's safety net: tier-1 bytes, skipped planes
+            assert i < len(body) and body[i] == 2, seq
+            i += 1
+        iterations += 1
+    assert 1 <= iterations <= 8, seq
+
+
 @pytest.mark.gpu
 def test_split_band_only_upload(encoder):
     img = im.synth_u16(1500, 800, comps=1, seed=8)
