@@ -42,6 +42,14 @@ extern "C" {
 #define JP2HIP_FORMAT_JP2 1
 #define JP2HIP_FORMAT_JPX 2 /* what a ".jpx" output name asks Kakadu for */
 
+/* jp2hip_recipe.progression: the packet order inside a tile (SGcod of COD,
+ * ISO/IEC 15444-1 Table A.16).  L layer, R resolution, C component, P position. */
+#define JP2HIP_ORDER_LRCP 0
+#define JP2HIP_ORDER_RLCP 1
+#define JP2HIP_ORDER_RPCL 2 /* the Bucketeer recipe's, and jp2hip_recipe_init's */
+#define JP2HIP_ORDER_PCRL 3
+#define JP2HIP_ORDER_CPRL 4
+
 typedef struct jp2hip_ctx jp2hip_ctx;
 
 typedef struct jp2hip_config {
@@ -63,10 +71,14 @@ typedef struct jp2hip_recipe {
                              /*   0..16 entries (0: one precinct), each 0..15, */
                              /*   0 only for the lowest resolution             */
     int32_t prec_h_log2[16];
-    int32_t progression;     /* Corder=RPCL (2); the only order implemented    */
+    int32_t progression;     /* Corder=RPCL: JP2HIP_ORDER_* (the COD value);   */
+                             /* the order moves the packets inside a tile,     */
+                             /* their Nsop and the PLT, never a packet's bytes */
     int32_t sop, eph;        /* Cuse_sop=yes Cuse_eph=yes                      */
     int32_t plt;             /* ORGgen_plt=yes                                 */
-    int32_t tparts_r;        /* ORGtparts=R                                    */
+    int32_t tparts_r;        /* ORGtparts=R: a tile-part per resolution; only  */
+                             /* with a resolution-major order (RLCP, RPCL),    */
+                             /* refused with LRCP, PCRL, CPRL; 0: one per tile */
     int32_t guard_bits;      /* 1 (0..7: three bits of Sqcd)                   */
     int32_t reversible;      /* Creversible=yes -> 5/3 + RCT, else 9/7 + ICT   */
     int32_t mct;             /* colour transform on components 0..2            */
@@ -386,6 +398,18 @@ int64_t jp2hip_tiff_pixels(const char *tiff_path_utf8);
 int jp2hip_split_thresholds(const uint64_t *keys, const int64_t *cum, int64_t nseg,
                             const int64_t *budgets, int32_t layers, const jp2hip_split *split,
                             uint64_t *K);
+
+/* Host-only: the packets of tile `tile` (raster index) of a width x height
+ * image of `components` x `bits`-bit samples, in the order recipe->progression
+ * sends them -- the function the encodes lay their tile-parts out with,
+ * exported for tests.  Entry s names the s-th packet as p * layers + l: layer
+ * l of the tile's p-th precinct counted in (resolution, precinct row, precinct
+ * column, component) order, the order the packets are stored in (so RPCL
+ * gives 0, 1, 2, ...).  Returns the tile's packet count and writes the first
+ * min(count, cap) entries to seq (which may be NULL when cap is 0), or < 0
+ * with jp2hip_last_error() for a recipe or geometry the encodes refuse. */
+int64_t jp2hip_packet_sequence(int32_t width, int32_t height, int32_t components, int32_t bits,
+                               const jp2hip_recipe *recipe, int32_t tile, uint32_t *seq, int64_t cap);
 
 /* ------------------------------------------------------------------------
  * Batch path: one GPU's work queue for a CSV batch.

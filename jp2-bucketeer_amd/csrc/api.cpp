@@ -318,6 +318,21 @@ int64_t jp2hip_file_header(const jp2hip_layout *layout, int32_t format, uint64_t
     return (int64_t)n;
 }
 
+int64_t jp2hip_packet_sequence(int32_t width, int32_t height, int32_t components, int32_t bits,
+                               const jp2hip_recipe *recipe, int32_t tile, uint32_t *seq, int64_t cap) {
+    if (!recipe || cap < 0 || (cap > 0 && !seq)) return fail("null recipe, or no room for the sequence");
+    // the plan an encode of this image builds (its refusals included), then
+    // the function its tier-2 tables take the order from
+    jp2hip::Plan plan;
+    std::string err;
+    if (!jp2hip::build_plan(plan, *recipe, width, height, components, bits, err)) return fail(err);
+    if (tile < 0 || tile >= plan.ntx * plan.nty) return fail("tile index outside the image's tiles");
+    std::vector<uint32_t> s;
+    jp2hip::packet_sequence(plan, tile, s);
+    std::copy(s.begin(), s.begin() + (ptrdiff_t)std::min<int64_t>(cap, (int64_t)s.size()), seq);
+    return (int64_t)s.size();
+}
+
 int jp2hip_encode_device(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *layout,
                          int conversion, const jp2hip_recipe *recipe, uint8_t **out, size_t *out_len,
                          jp2hip_stats *stats) {

@@ -47,7 +47,7 @@ struct FrontJob;  // front.hip
     X(grptab) X(gtot)                                                                                         \
     /* device tier-2 (t2_device.hip) */                                                                       \
     X(hdist) X(rstate) X(t2ticket) X(t2prec) X(t2tp) X(t2tt) X(t2lblock) X(t2incl) X(t2pklen) X(t2pkoff)      \
-    X(t2tplen) X(t2tphdr) X(t2tpoff) X(t2blkdst) X(t2out) X(t2sum)                                            \
+    X(t2tplen) X(t2tphdr) X(t2tpoff) X(t2blkdst) X(t2out) X(t2sum) X(t2seq)                                   \
     /* S1b sample expansion (expand.hip): the 8-bit copy, its unit offsets and the colour table */           \
     X(expanded) X(exoff) X(exlut)
 
@@ -258,6 +258,7 @@ class GpuEncoder {
     RateState *d_rs_out = nullptr;  // its device address
     int t2_nprec = 0, t2_ntp = 0;
     bool t2_wave = true;  // precincts of <= 64 blocks: k_t2_wave (layer assignment fused in)
+    bool t2_seq = false;  // a progression order other than RPCL: t2seq holds its forward map
     uint64_t front_gen = 0, t2_gen = 0;  // plan generation whose tables are resident
     T2Summary *h_sum = nullptr;
     int64_t *h_tot = nullptr;  // pinned [8]: t1 total, -, k_t1_mq span[2], unpack error, segment tail[2]

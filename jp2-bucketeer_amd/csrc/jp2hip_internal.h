@@ -150,17 +150,25 @@ void make_subplan(const Plan &full, int tr0, int tr1, Plan &sub);
 
 // --------------------------------------------------------------------------
 // Device tier-2 (t2_device.hip).  The host lays out, once per encode, the precincts
-// of the tiles being coded in packet order (tile, resolution, py, px,
-// component; RPCL) and the tile-parts in code-stream order (-flush_period
-// stripes); the kernels code every packet header, size the tile-parts and
-// write the code-stream in HBM.  Packet k of precinct p is packet p * L + k.
+// of the tiles being coded in storage order (tile, resolution, py, px,
+// component: the RPCL packet order) and the tile-parts in code-stream order
+// (-flush_period stripes); the kernels code every packet header, size the
+// tile-parts and write the code-stream in HBM.  Packet k of precinct p is
+// stored as packet p * L + k in every progression order: the order moves only
+// where a packet lies in its tile-part (T2Tables::seq), its Nsop and its place
+// in the PLT, never its bytes.
 // --------------------------------------------------------------------------
 struct PrecDesc {
     int32_t first[3];        // first code-block (encode-local index) of each precinct-band
     uint16_t ncw[3], nch[3]; // code-block grid of each precinct-band
     int32_t tt_off;          // tag-tree node scratch: (inclusion, zero bit-planes) per band
     int32_t nsop0;           // SOP sequence number of the precinct's first packet in its tile
-    uint8_t nb, pad0, pad1, pad2;
+    uint8_t nb, pad0;
+    // Nsop of the layer-l packet = nsop0 + l * nsop_step (mod 65536, so the
+    // step's low 16 bits are all that count): 1 where layers are innermost
+    // (RPCL, PCRL, CPRL), the resolution's packets per layer in RLCP, the
+    // tile's in LRCP
+    uint16_t nsop_step;
 };
 static_assert(sizeof(PrecDesc) == 36, "PrecDesc layout");
 struct TpDesc {
@@ -170,12 +178,23 @@ struct TpDesc {
 struct T2Tables {
     std::vector<PrecDesc> prec;
     std::vector<TpDesc> tp;   // code-stream order
+    // Forward map of the progression order: a tile-part stores its packets at
+    // [prec0 * L, (prec0 + nprec) * L), and the s-th packet it sends is packet
+    // seq[prec0 * L + s].  Empty = identity (RPCL: storage order is sequence
+    // order).
+    std::vector<uint32_t> seq;
     int64_t tt_nodes = 0;
     int max_prec_blocks = 0;  // code-blocks of the largest precinct
 };
 // Tables for tiles [tile0, tile1) of `P` (blocks rebased by -block0: a
 // tile-split rank's blocks are its sub-plan's).
 void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T);
+// Tile t's packets in the order rc.progression sends them (B.12.1; no
+// component is subsampled): each entry the packet's storage index within the
+// tile, p * L + l for the tile's p-th precinct in (resolution, py, px,
+// component) order.  RPCL gives the identity.  A tile-part per resolution
+// (RLCP, RPCL) takes its packets as a contiguous run of this sequence.
+void packet_sequence(const Plan &P, int t, std::vector<uint32_t> &seq);
 // What the host reads back after a tier-2 sizing pass (one D2H per pass).
 struct T2Summary {
     int64_t part_bytes;               // tile-parts of the tiles coded (SOT .. last packet)

@@ -187,7 +187,18 @@ bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits
         err = "unsupported image geometry (1-4 components, 8 or 16 bits)";
         return false;
     }
-    if (rc.progression != 2) { err = "only RPCL progression is implemented"; return false; }
+    if (rc.progression < JP2HIP_ORDER_LRCP || rc.progression > JP2HIP_ORDER_CPRL) {
+        err = "progression must be 0..4 (LRCP, RLCP, RPCL, PCRL, CPRL)";
+        return false;
+    }
+    // a tile-part per resolution holds a run of the tile's packets only where
+    // the resolution is the outermost loop
+    if (rc.tparts_r && rc.progression != JP2HIP_ORDER_RLCP && rc.progression != JP2HIP_ORDER_RPCL) {
+        static const char *const kOrder[] = {"LRCP", "RLCP", "RPCL", "PCRL", "CPRL"};
+        err = std::string("tparts_r = 1 (a tile-part per resolution) needs a resolution-major progression "
+                          "(RLCP or RPCL), not ") + kOrder[rc.progression];
+        return false;
+    }
     if (rc.levels < 0 || rc.levels > kMaxLevels || rc.layers < 1 || rc.layers > kMaxLayers) {
         err = "levels must be 0..12 and layers 1..32";
         return false;

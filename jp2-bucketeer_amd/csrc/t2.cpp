@@ -8,6 +8,9 @@
 // per resolution (ORGtparts=R) each carrying a PLT marker (ORGgen_plt=yes),
 // tile-parts in -flush_period stripe order, COM markers in Kakadu's layout.
 // The layout is the one oracle/jp2_oracle.c writes (write_codestream).
+// The other progression orders (LRCP, RLCP, PCRL, CPRL) keep the packets and
+// their storage; packet_sequence says in which order a tile sends them, and
+// t2_tables turns that into the device's forward map and SOP numbers.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -118,11 +121,82 @@ static int64_t tree_nodes(int w, int h) {
     }
 }
 
+void packet_sequence(const Plan &P, int t, std::vector<uint32_t> &seq) {
+    const jp2hip_recipe &rc = P.rc;
+    const int Lv = rc.levels, L = rc.layers, order = rc.progression;
+    const Tile &Tl = P.tiles[(size_t)t];
+    // the tile's precincts in storage order, each with what the orders sort
+    // by: resolution, component, raster index in the resolution's precinct
+    // grid, and its position on the reference grid (B.12.1.3-5 with no
+    // subsampling: the precinct's corner, or the tile's where that lies
+    // before it)
+    struct Prec {
+        int32_t r, c, raster;
+        int64_t x, y;
+        uint32_t p;
+    };
+    std::vector<Prec> pv;
+    for (int r = 0; r <= Lv; r++) {
+        const Resolution &R0 = Tl.tc[0].res[r];
+        if (R0.npx * R0.npy == 0) continue;
+        const int sh = Lv - r, ppx = prec_log2(rc, r, false), ppy = prec_log2(rc, r, true);
+        const int64_t px0 = ((int64_t)Tl.tx0 >> sh) >> ppx, py0 = ((int64_t)Tl.ty0 >> sh) >> ppy;
+        for (int py = 0; py < R0.npy; py++)
+            for (int px = 0; px < R0.npx; px++)
+                for (int c = 0; c < P.nc; c++) {
+                    Prec e;
+                    e.r = r;
+                    e.c = c;
+                    e.raster = py * R0.npx + px;
+                    e.x = std::max<int64_t>(Tl.tx0, (px0 + px) << (ppx + sh));
+                    e.y = std::max<int64_t>(Tl.ty0, (py0 + py) << (ppy + sh));
+                    e.p = (uint32_t)pv.size();
+                    pv.push_back(e);
+                }
+    }
+    seq.clear();
+    seq.reserve(pv.size() * (size_t)L);
+    if (order == JP2HIP_ORDER_LRCP || order == JP2HIP_ORDER_RLCP) {
+        // (r, c, raster) is the order inside a layer of both; storage order
+        // is (r, raster, c)
+        std::stable_sort(pv.begin(), pv.end(), [](const Prec &a, const Prec &b) {
+            return a.r != b.r ? a.r < b.r : (a.c != b.c ? a.c < b.c : a.raster < b.raster);
+        });
+        if (order == JP2HIP_ORDER_LRCP) {
+            for (int l = 0; l < L; l++)
+                for (const Prec &e : pv) seq.push_back(e.p * (uint32_t)L + (uint32_t)l);
+        } else {
+            for (size_t i = 0; i < pv.size();) {
+                size_t j = i;
+                while (j < pv.size() && pv[j].r == pv[i].r) j++;
+                for (int l = 0; l < L; l++)
+                    for (size_t k = i; k < j; k++) seq.push_back(pv[k].p * (uint32_t)L + (uint32_t)l);
+                i = j;
+            }
+        }
+        return;
+    }
+    if (order == JP2HIP_ORDER_PCRL)
+        std::stable_sort(pv.begin(), pv.end(), [](const Prec &a, const Prec &b) {
+            return a.y != b.y ? a.y < b.y : (a.x != b.x ? a.x < b.x : (a.c != b.c ? a.c < b.c : a.r < b.r));
+        });
+    else if (order == JP2HIP_ORDER_CPRL)
+        std::stable_sort(pv.begin(), pv.end(), [](const Prec &a, const Prec &b) {
+            return a.c != b.c ? a.c < b.c : (a.y != b.y ? a.y < b.y : (a.x != b.x ? a.x < b.x : a.r < b.r));
+        });
+    // (RPCL: storage order)
+    for (const Prec &e : pv)
+        for (int l = 0; l < L; l++) seq.push_back(e.p * (uint32_t)L + (uint32_t)l);
+}
+
 void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
     const jp2hip_recipe &rc = P.rc;
     const int Lv = rc.levels, L = rc.layers;
+    const bool resequence = rc.progression != JP2HIP_ORDER_RPCL;
+    std::vector<uint32_t> tseq, pos;
     T.prec.clear();
     T.tp.clear();
+    T.seq.clear();
     T.tt_nodes = 0;
     T.max_prec_blocks = 0;
     // tile-parts per tile, in tile order first
@@ -130,6 +204,7 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
     for (int t = tile0; t < tile1; t++) {
         const Tile &Tl = P.tiles[t];
         int nsop = 0;
+        const size_t tile_prec0 = T.prec.size();
         std::vector<TpDesc> &tps = per_tile[(size_t)(t - tile0)];
         for (int r = 0; r <= Lv; r++) {
             const Resolution &R0 = Tl.tc[0].res[r];
@@ -145,6 +220,7 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
                         d.nb = (uint8_t)pr.nb;
                         d.tt_off = (int32_t)T.tt_nodes;
                         d.nsop0 = nsop;
+                        d.nsop_step = 1;
                         int blocks = 0;
                         for (int bi = 0; bi < pr.nb; bi++) {
                             const PrecBand &pb = pr.pb[bi];
@@ -161,6 +237,23 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
                     }
         }
         for (TpDesc &tp : tps) tp.tnsot = (&tp == &tps.back()) ? (int32_t)tps.size() : 0;
+        if (resequence) {
+            // another order: the tile's sequence (its tile-parts take runs of
+            // it: one part, or RLCP's part per resolution), and each packet's
+            // place in it as its Nsop -- nsop0 for layer 0, then nsop_step a
+            // layer: 1 where layers are innermost, else the packets of one
+            // layer of the resolution (RLCP) or of the tile (LRCP)
+            packet_sequence(P, t, tseq);
+            pos.resize(tseq.size());
+            for (size_t s = 0; s < tseq.size(); s++) pos[tseq[s]] = (uint32_t)s;
+            for (size_t i = tile_prec0; i < T.prec.size(); i++) {
+                const size_t k = (i - tile_prec0) * (size_t)L;
+                T.prec[i].nsop0 = (int32_t)pos[k];
+                T.prec[i].nsop_step = L > 1 ? (uint16_t)(pos[k + 1] - pos[k]) : 1;
+            }
+            const uint32_t base = (uint32_t)(tile_prec0 * (size_t)L);
+            for (uint32_t s : tseq) T.seq.push_back(base + s);
+        }
     }
     // code-stream order: per -flush_period stripe, resolution 0 of every tile,
     // then resolution 1, ... (test.jpx; t2_emit_part does the same on the host)

@@ -6,6 +6,10 @@
 // per resolution (ORGtparts=R) with a PLT marker (ORGgen_plt=yes), tile-parts
 // in -flush_period stripe order (t2_tables, test.jpx).  The byte layout is
 // the oracle's (oracle/jp2_oracle.c encode_packet / write_codestream).
+// Another progression order (LRCP, RLCP, PCRL, CPRL) changes no packet and
+// no storage index: the tile-part kernels (tpart_size, k_t2_tp_emit) take
+// the packets in the order of the forward map T2Args::seq, and a packet's
+// Nsop is PrecDesc's nsop0 + layer * nsop_step.
 //
 // Parallel structure.  A precinct's L packets share state (tag trees, each
 // block's Lblock and inclusion layer); precincts are independent (C2: 2 880
@@ -59,6 +63,10 @@ struct T2Args {
     uint32_t *tt;           // tag-tree nodes: value | low << 8 | known << 16
     int8_t *lblock, *incl;  // per block coding state
     uint32_t *pk_len;       // [nprec * L] SOP + header + EPH + body
+    // the progression order's forward map (T2Tables::seq): the s-th packet of
+    // the tile-part whose packets are stored at [p0, p1) is packet seq[p0 + s];
+    // null = RPCL, where it is packet p0 + s
+    const uint32_t *seq;
     uint32_t *tp_len;       // [ntp] Psot
     uint32_t *tp_hdr;       // [ntp] SOT + PLT + SOD
     uint64_t *tp_off;       // [ntp] offset of the tile-part in the part
@@ -235,7 +243,7 @@ __global__ void __launch_bounds__(64) k_t2_code(T2Args a) {
         if (EMIT) {
             o = a.out + a.pk_off[pk];
             if (a.sop) {
-                const uint32_t ns = (uint32_t)(d.nsop0 + l) & 0xFFFFu;
+                const uint32_t ns = (uint32_t)(d.nsop0 + l * (int)d.nsop_step) & 0xFFFFu;
                 o[0] = 0xFF; o[1] = 0x91; o[2] = 0; o[3] = 4; o[4] = (uint8_t)(ns >> 8); o[5] = (uint8_t)ns;
                 o += 6;
             }
@@ -613,7 +621,7 @@ __device__ __forceinline__ void t2_wave_precinct(const T2Args &a, const T2LaneSh
                 if (EMIT) {
                     o = a.out + a.pk_off[pk];
                     if (a.sop) {
-                        const uint32_t ns = (uint32_t)(d.nsop0 + l0 + lane) & 0xFFFFu;
+                        const uint32_t ns = (uint32_t)(d.nsop0 + (l0 + lane) * (int)d.nsop_step) & 0xFFFFu;
                         o[0] = 0xFF; o[1] = 0x91; o[2] = 0; o[3] = 4; o[4] = (uint8_t)(ns >> 8); o[5] = (uint8_t)ns;
                         o += 6;
                     }
@@ -682,14 +690,29 @@ struct RateStepArgs {
     RateState *out_rs;
     T2Summary *out_sum;
 };
-__device__ __forceinline__ void tpart_size(const T2Args &a, int t) {
+// Storage indices of the packets a tile-part sends at places i0 .. i0 + 7 of
+// [.., p1) (SEQ: through the forward map, 8 loads in flight; else the places
+// themselves).  SEQ is a kernel argument's null test: uniform over the grid.
+template <bool SEQ>
+__device__ __forceinline__ void seq_load8(const T2Args &a, size_t i0, size_t p1, size_t (&s8)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const size_t i = min(i0 + j, p1 - 1);
+        s8[j] = SEQ ? (size_t)a.seq[i] : i;
+    }
+}
+
+template <bool SEQ>
+__device__ __forceinline__ void tpart_size_seq(const T2Args &a, int t) {
     const TpDesc d = a.tps[t];
     const size_t p0 = (size_t)d.prec0 * a.L, p1 = (size_t)(d.prec0 + d.nprec) * a.L;
     uint64_t body = 0, plt = 0, seg = 0;
     for (size_t i0 = p0; i0 < p1; i0 += 8) {  // 8 lengths' loads in flight at a time
+        size_t s8[8];
+        seq_load8<SEQ>(a, i0, p1, s8);
         uint32_t l8[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) l8[j] = a.pk_len[min(i0 + j, p1 - 1)];
+        for (int j = 0; j < 8; j++) l8[j] = a.pk_len[s8[j]];
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const size_t i = i0 + j;
@@ -709,6 +732,10 @@ __device__ __forceinline__ void tpart_size(const T2Args &a, int t) {
     if (a.plt && p1 > p0) plt += 5 + seg;
     a.tp_hdr[t] = (uint32_t)(14 + plt);
     a.tp_len[t] = (uint32_t)(14 + plt + body);
+}
+__device__ __forceinline__ void tpart_size(const T2Args &a, int t) {
+    if (a.seq) tpart_size_seq<true>(a, t);
+    else tpart_size_seq<false>(a, t);
 }
 
 // One workgroup of kTotThreads: tile-part sizes (a thread per tile-part, or
@@ -878,10 +905,10 @@ __global__ void __launch_bounds__(64 * kT2Waves) k_t2_wave(T2Args a, T2TotalArgs
     t2_total_body<64 * kT2Waves, false>(a, ta, wsum, red);
 }
 
-// SOT + PLT + SOD of each tile-part, and where each of its packets starts
-__global__ void __launch_bounds__(64) k_t2_tp_emit(T2Args a) {
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.ntp) return;
+// SOT + PLT + SOD of each tile-part, and where each of its packets starts:
+// the packets in the order they are sent (SEQ: through the forward map)
+template <bool SEQ>
+__device__ __forceinline__ void tpart_emit(const T2Args &a, int t) {
     const TpDesc d = a.tps[t];
     uint8_t *p = a.out + a.base + a.tp_off[t];
     const uint32_t psot = a.tp_len[t];
@@ -901,9 +928,11 @@ __global__ void __launch_bounds__(64) k_t2_tp_emit(T2Args a) {
         p += 5;
         uint32_t seg = 0;
         while (i < p1) {
+            size_t s8[8];
+            seq_load8<SEQ>(a, i, p1, s8);
             uint32_t l8[8];
 #pragma unroll
-            for (int j = 0; j < 8; j++) l8[j] = a.pk_len[min(i + j, p1 - 1)];
+            for (int j = 0; j < 8; j++) l8[j] = a.pk_len[s8[j]];
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 if (i >= p1) break;
@@ -930,16 +959,24 @@ __global__ void __launch_bounds__(64) k_t2_tp_emit(T2Args a) {
     p += 2;
     uint64_t o = (uint64_t)(p - a.out);
     for (size_t i0 = p0; i0 < p1; i0 += 8) {
+        size_t s8[8];
+        seq_load8<SEQ>(a, i0, p1, s8);
         uint32_t l8[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) l8[j] = a.pk_len[min(i0 + j, p1 - 1)];
+        for (int j = 0; j < 8; j++) l8[j] = a.pk_len[s8[j]];
 #pragma unroll
         for (int j = 0; j < 8; j++)
             if (i0 + j < p1) {
-                a.pk_off[i0 + j] = o;
+                a.pk_off[s8[j]] = o;
                 o += l8[j];
             }
     }
+}
+__global__ void __launch_bounds__(64) k_t2_tp_emit(T2Args a) {
+    const int t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= a.ntp) return;
+    if (a.seq) tpart_emit<true>(a, t);
+    else tpart_emit<false>(a, t);
 }
 
 // code-block bytes into the packet bodies: one wave per block, its layer
@@ -1239,6 +1276,7 @@ T2Args GpuEncoder::t2_args(const Plan &plan) const {
     a.lblock = (int8_t *)t2lblock.ptr;
     a.incl = (int8_t *)t2incl.ptr;
     a.pk_len = (uint32_t *)t2pklen.ptr;
+    a.seq = t2_seq ? (const uint32_t *)t2seq.ptr : nullptr;
     a.tp_len = (uint32_t *)t2tplen.ptr;
     a.tp_hdr = (uint32_t *)t2tphdr.ptr;
     a.tp_off = (uint64_t *)t2tpoff.ptr;
@@ -1254,6 +1292,7 @@ bool GpuEncoder::t2_load(const Plan &plan, const T2Tables &T, std::string &err) 
     const int L = plan.rc.layers;
     t2_nprec = (int)T.prec.size();
     t2_ntp = (int)T.tp.size();
+    t2_seq = !T.seq.empty();  // (else RPCL: the kernels walk the packets as they are stored)
     // k_t2_wave (else the serial k_t2_code + k_apply)
     int max_mb = 0;
     for (const BlockDesc &bd : plan.blocks) max_mb = std::max(max_mb, (int)bd.Mb);
@@ -1264,7 +1303,8 @@ bool GpuEncoder::t2_load(const Plan &plan, const T2Tables &T, std::string &err) 
         !ensure<int8_t>(t2incl, nb, err) || !ensure<uint32_t>(t2pklen, npk, err) ||
         !ensure<uint64_t>(t2pkoff, npk, err) || !ensure<uint32_t>(t2tplen, T.tp.size(), err) ||
         !ensure<uint32_t>(t2tphdr, T.tp.size(), err) || !ensure<uint64_t>(t2tpoff, T.tp.size(), err) ||
-        !ensure<uint64_t>(t2blkdst, (size_t)nb * L, err) || !ensure<T2Summary>(t2sum, 1, err))
+        !ensure<uint64_t>(t2blkdst, (size_t)nb * L, err) || !ensure<T2Summary>(t2sum, 1, err) ||
+        (t2_seq && !ensure<uint32_t>(t2seq, T.seq.size(), err)))
         return false;
     if (!h_sum) HIPCHECK(hipHostMalloc((void **)&h_sum, sizeof(T2Summary), hipHostMallocDefault));
     if (!t2ticket.ptr) {  // k_t2_wave<false>'s arrival counter: zero once, left zero by every launch
@@ -1274,7 +1314,8 @@ bool GpuEncoder::t2_load(const Plan &plan, const T2Tables &T, std::string &err) 
     if (plan.gen && plan.gen == t2_gen) return true;  // resident (same plan, same tables)
     t2_gen = 0;
     if (!h2d(t2prec.ptr, T.prec.data(), sizeof(PrecDesc) * T.prec.size(), err) ||
-        !h2d(t2tp.ptr, T.tp.data(), sizeof(TpDesc) * T.tp.size(), err))
+        !h2d(t2tp.ptr, T.tp.data(), sizeof(TpDesc) * T.tp.size(), err) ||
+        (t2_seq && !h2d(t2seq.ptr, T.seq.data(), sizeof(uint32_t) * T.seq.size(), err)))
         return false;
     t2_gen = plan.gen;
     return true;

@@ -19,6 +19,8 @@ LOSSLESS = 1   # Conversion.LOSSLESS (Conversion.java:9)
 FORMAT_J2K, FORMAT_JP2, FORMAT_JPX = 0, 1, 2
 # Layout.photometric (JP2HIP_PHOTO_*)
 PHOTO_DEFAULT, PHOTO_WHITE_IS_ZERO, PHOTO_PALETTE = 0, 1, 2
+# Recipe.progression (JP2HIP_ORDER_*: COD's progression order)
+ORDER_LRCP, ORDER_RLCP, ORDER_RPCL, ORDER_PCRL, ORDER_CPRL = 0, 1, 2, 3, 4
 
 
 class Jp2hipError(OSError):
@@ -126,6 +128,8 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            # tile-split path (csrc/split.cpp, encode.cpp, split_host.cpp; bound in jp2hip.split)
            "jp2hip_split_rows", "jp2hip_encode_device_split", "jp2hip_split_thresholds",
            "jp2hip_split_peers", "jp2hip_tiff_pixels", "jp2hip_env_check",
+           # the progression order's packet sequence (api.cpp; host only)
+           "jp2hip_packet_sequence",
            # device-memory policy (api.cpp; csrc/context.h EncodeEnd)
            "jp2hip_device_bytes", "jp2hip_set_memory_limits", "jp2hip_device_memory", "jp2hip_dma_engines")
 
@@ -185,6 +189,9 @@ def lib():
     L.jp2hip_split_thresholds.argtypes = [POINTER(c_uint64), POINTER(c_int64), c_int64,
                                           POINTER(c_int64), c_int32, POINTER(Split),
                                           POINTER(c_uint64)]
+    L.jp2hip_packet_sequence.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(Recipe), c_int32,
+                                         POINTER(c_uint32), c_int64]
+    L.jp2hip_packet_sequence.restype = c_int64
     L.jp2hip_device_bytes.argtypes = [c_void_p]
     L.jp2hip_device_bytes.restype = c_int64
     L.jp2hip_set_memory_limits.argtypes = [c_void_p, c_int64, c_int64]
@@ -270,6 +277,20 @@ def recipe(conversion: int, **overrides) -> Recipe:
         else:
             setattr(r, k, v)
     return r
+
+
+def packet_sequence(width: int, height: int, components: int, bits: int, rcp: Recipe, tile: int) -> list[int]:
+    """The packets of tile `tile` in the order ``rcp.progression`` sends them
+    (jp2hip_packet_sequence; no GPU): entry s is ``p * layers + l`` for layer
+    l of the tile's p-th precinct in (resolution, row, column, component)
+    order -- RPCL gives 0, 1, 2, ...  Raises for a recipe the encodes refuse."""
+    n = int(lib().jp2hip_packet_sequence(width, height, components, bits, byref(rcp), tile, None, 0))
+    if n < 0:
+        raise Jp2hipError(last_error())
+    buf = (c_uint32 * max(1, n))()
+    if int(lib().jp2hip_packet_sequence(width, height, components, bits, byref(rcp), tile, buf, n)) != n:
+        raise Jp2hipError(last_error())
+    return list(buf[:n])
 
 
 def tiff_layout(data: bytes):
