@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "dwt_fetch.h"
 #include "gpu_encoder.h"
 
 namespace jp2hip {
@@ -139,6 +140,8 @@ struct DwtBandArgs {
     const int32_t *tc_w, *tc_h;
     int level, R;
     int ragged;  // some tile width is not a multiple of 16 (k_dwt_l1s second launch)
+    int px_fetch;      // k_dwt_l1s: chunky pixels are loaded with one access each (dwt_fetch.h)
+    uint64_t src_end;  // ... none of which ends beyond this source offset
     QuantTab qt;
 };
 
@@ -202,6 +205,44 @@ __device__ __forceinline__ void lift_regs(int32_t (&v)[NR], int y0, int H) {
             const int im = i > 0 ? i - 1 : i + 1, ip = i + 1 < NR ? i + 1 : i - 1;
             const int32_t l = (!interior && y == 0) ? v[ip] : v[im];
             const int32_t r = (interior || y + 1 < H) ? v[ip] : v[im];
+            if (REV) {
+                if (s == 0) v[i] -= (l + r) >> 1;
+                else v[i] += (l + r + 2) >> 2;
+            } else {
+                const float cf = s == 0 ? A97 : (s == 1 ? B97 : (s == 2 ? G97 : D97));
+                float t = __int_as_float(l) + __int_as_float(r);
+                t = cf * t;
+                v[i] = __float_as_int(__int_as_float(v[i]) + t);
+            }
+        }
+    }
+}
+
+// lift_regs for a wave-uniform window (k_dwt_band: y0 is the workgroup's): an
+// interior window lifts straight-line code; one that touches row 0 or H-1
+// selects per value on a copy of y0 held in a vector register, so each
+// condition is a compare in front of its select.  (As uniform conditions
+// the compiler computed all 2 NR of them ahead as lane masks in scalar
+// register pairs, and with the row pointers they spilled ~100 scalar
+// registers to vector lanes.)  Same expressions, same order.
+template <bool REV, int NR>
+__device__ __forceinline__ void lift_regs_u(int32_t (&v)[NR], int y0, int H) {
+    const int nsteps = REV ? 2 : 4;
+    const bool interior = y0 >= 0 && y0 + NR <= H;
+    int yv = y0;
+    if (!interior) asm volatile("" : "+v"(yv));
+#pragma unroll
+    for (int s = 0; s < nsteps; s++) {
+        const int par = (s & 1) ? 0 : 1;
+#pragma unroll
+        for (int i = par; i < NR; i += 2) {
+            const int im = i > 0 ? i - 1 : i + 1, ip = i + 1 < NR ? i + 1 : i - 1;
+            int32_t l = v[im], r = v[ip];
+            if (!interior) {
+                const int y = yv + i;
+                l = y == 0 ? v[ip] : v[im];
+                r = y + 1 < H ? v[ip] : v[im];
+            }
             if (REV) {
                 if (s == 0) v[i] -= (l + r) >> 1;
                 else v[i] += (l + r + 2) >> 2;
@@ -505,26 +546,42 @@ __global__ void __launch_bounds__(NT) k_dwt_band(DwtBandArgs a) {
     for (int x = tid; x < W; x += NT) {
         int32_t v[NR];
         // every row load issues before any is used: rows outside the band
-        // read a clamped (valid) row and are zeroed after (a load under a
-        // per-row branch was waited for before the next one issued)
+        // read a clamped (valid) row (a load under a per-row branch was
+        // waited for before the next one issued).  What such a row holds
+        // never matters: the symmetric extension keeps rows inside [0, H)
+        // from reading it (lift_regs).  Without ingest the row and LDS
+        // offsets are formed per lane from vector copies of y0 and ld: as
+        // uniform values all NR row pointers and RB LDS offsets were held in
+        // scalar registers at once, and spilled (lift_regs_u).
+        if constexpr (INGEST) {
 #pragma unroll
-        for (int i = 0; i < NR; i++) v[i] = band_load<REV, INGEST>(a, tc, min(max(y0 + i, 0), H - 1), x);
+            for (int i = 0; i < NR; i++) v[i] = band_load<REV, INGEST>(a, tc, min(max(y0 + i, 0), H - 1), x);
+        } else {
+            const int32_t *sp = (const int32_t *)a.src + (size_t)tc * a.src_tc + x;
+            int yv = y0;
+            asm volatile("" : "+v"(yv));
 #pragma unroll
-        for (int i = 0; i < NR; i++) {
-            const int y = y0 + i;
-            v[i] = (y >= 0 && y < H) ? v[i] : 0;
+            for (int i = 0; i < NR; i++) v[i] = sp[(size_t)min(max(yv + i, 0), H - 1) * a.src_stride];
         }
         if (H > 1) {
-            lift_regs<REV, NR>(v, y0, H);
+            if constexpr (INGEST) lift_regs<REV, NR>(v, y0, H);
+            else lift_regs_u<REV, NR>(v, y0, H);
             if (!REV) {
 #pragma unroll
                 for (int i = kDwtHalo; i < kDwtHalo + RB; i++)
                     v[i] = __float_as_int(__int_as_float(v[i]) * ((i & 1) ? K97 : INVK97));
             }
         }
+        int ldv = ld, nkv = nkeep;
+        if constexpr (!INGEST) asm volatile("" : "+v"(ldv), "+v"(nkv));
+        if (nkeep == RB) {  // every band but a region's last
 #pragma unroll
-        for (int i = 0; i < RB; i++)
-            if (i < nkeep) lds[kPadL + i * ld + x] = v[kDwtHalo + i];
+            for (int i = 0; i < RB; i++) lds[kPadL + i * ldv + x] = v[kDwtHalo + i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < RB; i++)
+                if (i < nkv) lds[kPadL + i * ldv + x] = v[kDwtHalo + i];
+        }
     }
     __syncthreads();
     // ---- horizontal lifting, scaling and de-interleaved write ----
@@ -660,7 +717,8 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
 // The vertical lifting runs as a pipeline down the band instead of over a
 // window with a halo per 8 rows: at row pair (m-1, m) step k updates row
 // m-1-k (k = 0..NS-1), after which rows m-NS and m-NS+1 are final, so each
-// TIFF row is read and lifted once (plus NS rows above and below the band).
+// TIFF row is read and lifted once (plus NS rows above and below the band),
+// a chunky pixel with one access for all its samples (dwt_fetch.h).
 // Every 8 final rows go through LDS for the horizontal lifting and the
 // de-interleaved write (hlift_write).  Each sample sees the same expressions
 // in the same order as lift_regs / oracle fwd97_1d (bit-exact): an update
@@ -685,7 +743,7 @@ static_assert(kL1sPf >= 1 && kL1sPf <= 3, "JP2HIP_L1S_PF: 1..3");
 #ifndef JP2HIP_L1S_R
 #define JP2HIP_L1S_R 4  // rows per horizontal batch (4 or 8)
 #endif
-// (101 VGPRs, 4 waves per SIMD for the C2 variant; a budget for 5 --
+// (99 VGPRs, 4 waves per SIMD for the C2 variant; a budget for 5 --
 // amdgpu_waves_per_eu(5), 5 VGPRs spilled -- measured no faster: 146.7 vs
 // 146.4 us, profiles/r05/ab_select_fold.txt)
 #ifndef JP2HIP_L1S_CENSUS
@@ -706,7 +764,9 @@ __device__ unsigned long long g_l1s_census[8];  // phases 0..6, then waves
     do {            \
     } while (0)
 #endif
-template <bool REV, int NC, int CPT, int RB, bool ALIGNED>
+// PX: chunky sources whose pixels are loaded with one access each (bytes per
+// sample, 1 or 2; dwt_fetch.h); 0: planar sources, per sample.
+template <bool REV, int NC, int CPT, int RB, bool ALIGNED, int PX>
 __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1s(DwtBandArgs a) {
 #if JP2HIP_L1S_CENSUS
     uint64_t cz[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -732,6 +792,10 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1s(DwtBandArgs a) {
     const size_t row_bytes = (size_t)a.img_w * (a.planar == 2 ? 1 : NC) * bps;
     const int gx0 = (t % a.ntx) * a.tile_w, gy0 = a.row0 + (t / a.ntx) * a.tile_h;
     const bool mct = a.mct && NC >= 3;
+    // chunky sources: one access per pixel; bit 63 of a row's offset marks a
+    // row whose last access needs pulling back (dwt_fetch.h)
+    constexpr bool pxf = PX != 0;
+    constexpr uint64_t kRowPull = 1ull << 63;
     // byte offset of every streamed row (per component plane when planar),
     // looked up once: a row fetch is then plain loads with no dependent
     // global read in front of them, so they stay in flight across the
@@ -743,8 +807,10 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1s(DwtBandArgs a) {
             const int r = i / ncp, c = i - r * ncp;
             const int gy = gy0 + s + r;
             const int strip = gy / a.rps;
-            rowtab[i] = a.strip_off[a.planar == 2 ? (size_t)c * a.spp_strips + strip : (size_t)strip] +
-                        (size_t)(gy - strip * a.rps) * row_bytes;
+            uint64_t o = a.strip_off[a.planar == 2 ? (size_t)c * a.spp_strips + strip : (size_t)strip] +
+                         (size_t)(gy - strip * a.rps) * row_bytes;
+            if (pxf && row_needs_pullback(o, row_bytes, NC, bps, a.src_end)) o |= kRowPull;
+            rowtab[i] = o;
         }
         __syncthreads();
     }
@@ -756,13 +822,39 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1s(DwtBandArgs a) {
         for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int i = 0; i < NWIN; i++) w[j][c][i] = 0;
-    // raw (level-shifted) samples of the next kL1sPf row pairs, fetched
-    // ahead so the loads are in flight during the lifting of the rows before
-    // them: row r (counted from s-1) lives in slot r % (2 kL1sPf)
+    // raw source bits of the next kL1sPf row pairs, fetched ahead so the loads
+    // are in flight during the lifting of the rows before them: row r (counted
+    // from s-1) lives in slot r % (2 kL1sPf).  Chunky sources: the pixel's
+    // bytes as loaded by one access (words 0 and, for 8-byte pixels, 1);
+    // planar sources: one word per sample (a u8, or the u16 as stored).  The
+    // level shift and byte order wait for place(), so nothing uses a load
+    // until it is placed.
     int32_t pf[2 * kL1sPf][CPT][NC];
-    // raw sample bits only (a u8, or the u16 as stored): the level shift and
-    // byte order wait for place(), so nothing uses a load until it is placed
+    auto fetch_px = [&](int q) {  // chunky: one access per pixel (dwt_fetch.h)
+        constexpr int BPS = PX ? PX : 1, LB = px_load_bytes(NC, BPS);
+        const uint64_t r = rowtab[rnext];
+        const uint64_t ro = r & ~kRowPull;
+        rnext++;
+        // (a row whose last access would overrun the source -- the image's
+        // last row at most -- pulls that access back; the others never look)
+        const bool pull = (r & kRowPull) != 0;
+#pragma unroll
+        for (int j = 0; j < CPT; j++) {
+            const int x = min(tid + j * kDwtThreads, W - 1);  // columns past W repeat the last one
+            const uint64_t addr = ro + (size_t)(gx0 + x) * (NC * BPS);
+            uint32_t w0, w1;
+            if (pull) px_fetch<NC, BPS>(a.tif, addr, true, a.src_end, w0, w1);
+            else px_fetch<NC, BPS>(a.tif, addr, false, a.src_end, w0, w1);
+            pf[q][j][0] = (int32_t)w0;
+            if constexpr (LB == 8) pf[q][j][1] = (int32_t)w1;
+        }
+    };
     auto fetch = [&](int q) {  // the next row (s, s+1, ...) into pf[q]
+        if constexpr (pxf) {
+            fetch_px(q);
+            return;
+        }
+        // planar sources (and ones too small for a whole access): per sample
         const int ncp = a.planar == 2 ? NC : 1;
         uint64_t ro[NC];
 #pragma unroll
@@ -770,7 +862,7 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1s(DwtBandArgs a) {
         rnext++;
 #pragma unroll
         for (int j = 0; j < CPT; j++) {
-            const int x = min(tid + j * kDwtThreads, W - 1);  // columns past W repeat the last one
+            const int x = min(tid + j * kDwtThreads, W - 1);
             const size_t xo = a.planar == 2 ? (size_t)(gx0 + x) * bps : (size_t)(gx0 + x) * NC * bps;
 #pragma unroll
             for (int c = 0; c < NC; c++) {
@@ -779,33 +871,60 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1s(DwtBandArgs a) {
             }
         }
     };
-    auto place = [&](int q, int slot) {  // colour transform, into window slot `slot`
-#pragma unroll
-        for (int j = 0; j < CPT; j++) {
+    const float foff = (float)off;
+    // level shift and colour transform of one pixel's stored samples u[],
+    // into window slot `slot`.  Irreversible: the shifted sample is formed in
+    // f32 (px_shift_f32: the same float as converting the shifted integer).
+    auto place_px = [&](int j, int slot, const uint32_t (&u)[NC]) {
+        if (REV) {
             int32_t smp[NC];
 #pragma unroll
-            for (int c = 0; c < NC; c++) {
-                const uint32_t r = (uint32_t)pf[q][j][c];
-                const int32_t v = (a.bits != 8 && a.big_endian) ? (int32_t)(((r & 0xFFu) << 8) | (r >> 8)) : (int32_t)r;
-                smp[c] = v - off;
-            }
+            for (int c = 0; c < NC; c++) smp[c] = (int32_t)u[c] - off;
 #pragma unroll
-            for (int c = 0; c < NC; c++) w[j][c][slot] = REV ? smp[c] : __float_as_int((float)smp[c]);
+            for (int c = 0; c < NC; c++) w[j][c][slot] = smp[c];
             if constexpr (NC >= 3) if (mct) {
-                if (REV) {
-                    w[j][0][slot] = (smp[0] + 2 * smp[1] + smp[2]) >> 2;
-                    w[j][1][slot] = smp[2] - smp[1];
-                    w[j][2][slot] = smp[0] - smp[1];
+                w[j][0][slot] = (smp[0] + 2 * smp[1] + smp[2]) >> 2;
+                w[j][1][slot] = smp[2] - smp[1];
+                w[j][2][slot] = smp[0] - smp[1];
+            }
+        } else {
+            float fs[NC];
+#pragma unroll
+            for (int c = 0; c < NC; c++) fs[c] = px_shift_f32(u[c], foff);
+#pragma unroll
+            for (int c = 0; c < NC; c++) w[j][c][slot] = __float_as_int(fs[c]);
+            if constexpr (NC >= 3) if (mct) {
+                const float R = fs[0], G = fs[1], B = fs[2];
+                float f0 = 0.299f * R; f0 = f0 + 0.587f * G; f0 = f0 + 0.114f * B;
+                float f1 = -0.16875f * R; f1 = f1 - 0.33126f * G; f1 = f1 + 0.5f * B;
+                float f2 = 0.5f * R; f2 = f2 - 0.41869f * G; f2 = f2 - 0.08131f * B;
+                w[j][0][slot] = __float_as_int(f0);
+                w[j][1][slot] = __float_as_int(f1);
+                w[j][2][slot] = __float_as_int(f2);
+            }
+        }
+    };
+    auto place = [&](int q, int slot) {  // prefetch slot q into window slot `slot`
+#pragma unroll
+        for (int j = 0; j < CPT; j++) {
+            uint32_t u[NC];
+            if constexpr (pxf) {
+                const uint32_t w0 = (uint32_t)pf[q][j][0], w1 = NC >= 3 ? (uint32_t)pf[q][j][NC >= 3 ? 1 : 0] : 0u;
+                if (PX == 1) {
+#pragma unroll
+                    for (int c = 0; c < NC; c++) u[c] = px_sample8(w0, c);
                 } else {
-                    const float R = (float)smp[0], G = (float)smp[1], B = (float)smp[2];
-                    float f0 = 0.299f * R; f0 = f0 + 0.587f * G; f0 = f0 + 0.114f * B;
-                    float f1 = -0.16875f * R; f1 = f1 - 0.33126f * G; f1 = f1 + 0.5f * B;
-                    float f2 = 0.5f * R; f2 = f2 - 0.41869f * G; f2 = f2 - 0.08131f * B;
-                    w[j][0][slot] = __float_as_int(f0);
-                    w[j][1][slot] = __float_as_int(f1);
-                    w[j][2][slot] = __float_as_int(f2);
+#pragma unroll
+                    for (int c = 0; c < NC; c++) u[c] = px_sample16(w0, w1, c, a.big_endian != 0);
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    const uint32_t r = (uint32_t)pf[q][j][c];
+                    u[c] = (a.bits != 8 && a.big_endian) ? (((r & 0xFFu) << 8) | (r >> 8)) : r;
                 }
             }
+            place_px(j, slot, u);
         }
     };
     // rows s .. s + 2 kL1sPf - 2 ahead of the first iteration
@@ -1094,18 +1213,19 @@ static void launch_l1_nc(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &
     }
     hipLaunchKernelGGL((k_dwt_l1<REV, NC, 8>), g, dim3(kDwtThreads), lds, st, a);
 }
-template <bool REV, int NC, int CPT, int RB>
-static void launch_l1s_rb(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
+template <bool REV, int NC, int CPT, int PX>
+static void launch_l1s_px(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
+    constexpr int RB = JP2HIP_L1S_R;
     static bool wide = false;
     if (lds > (size_t)kDwtLdsWords * 4 && !wide) {
-        (void)hipFuncSetAttribute((const void *)k_dwt_l1s<REV, NC, CPT, RB, true>,
+        (void)hipFuncSetAttribute((const void *)k_dwt_l1s<REV, NC, CPT, RB, true, PX>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kDwtLdsWordsWide * 4);
-        (void)hipFuncSetAttribute((const void *)k_dwt_l1s<REV, NC, CPT, RB, false>,
+        (void)hipFuncSetAttribute((const void *)k_dwt_l1s<REV, NC, CPT, RB, false, PX>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, kDwtLdsWordsWide * 4);
         wide = true;
     }
-    hipLaunchKernelGGL((k_dwt_l1s<REV, NC, CPT, RB, true>), g, dim3(kDwtThreads), lds, st, a);
-    if (a.ragged) hipLaunchKernelGGL((k_dwt_l1s<REV, NC, CPT, RB, false>), g, dim3(kDwtThreads), lds, st, a);
+    hipLaunchKernelGGL((k_dwt_l1s<REV, NC, CPT, RB, true, PX>), g, dim3(kDwtThreads), lds, st, a);
+    if (a.ragged) hipLaunchKernelGGL((k_dwt_l1s<REV, NC, CPT, RB, false, PX>), g, dim3(kDwtThreads), lds, st, a);
 #if JP2HIP_L1S_CENSUS
     unsigned long long h[8];
     if (hipStreamSynchronize(st) == hipSuccess &&
@@ -1121,8 +1241,11 @@ static void launch_l1s_rb(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs 
 }
 template <bool REV, int NC, int CPT>
 static void launch_l1s_c(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    if (a.R == 8) launch_l1s_rb<REV, NC, CPT, 8>(g, lds, st, a);
-    else launch_l1s_rb<REV, NC, CPT, 4>(g, lds, st, a);
+    // one access per chunky pixel unless the source is planar (or smaller than an access)
+    const int px = (a.planar != 2 && a.px_fetch) ? a.bits >> 3 : 0;
+    if (px == 1) launch_l1s_px<REV, NC, CPT, 1>(g, lds, st, a);
+    else if (px == 2) launch_l1s_px<REV, NC, CPT, 2>(g, lds, st, a);
+    else launch_l1s_px<REV, NC, CPT, 0>(g, lds, st, a);
 }
 template <bool REV, int NC>
 static void launch_l1s_nc(int cpt, dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
@@ -1159,6 +1282,8 @@ bool launch_dwt(const DwtLaunch &p, hipStream_t st) {
     a.plane = (size_t)p.plane_w * p.plane_h;
     a.tc_w = p.tc_w; a.tc_h = p.tc_h;
     a.ragged = (p.tile_w & 15) || (p.last_tile_w & 15) || p.last_tile_w == 1;
+    a.src_end = p.src_end;
+    a.px_fetch = px_fetch_usable(p.src_end);
     const int ll_stride = (p.plane_w + 1) / 2;
     const size_t ll_tc = (size_t)ll_stride * ((p.plane_h + 1) / 2);
     void *scratch[2] = {p.scratch0, p.scratch1};

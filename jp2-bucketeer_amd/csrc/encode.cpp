@@ -61,12 +61,14 @@ jp2hip_recipe recipe_of(const jp2hip_recipe *recipe, int conversion) {
 namespace {
 
 // A rate-driven encode's target (bytes): the floor(rate * W * H / 8) the
-// oracle's predict_and_code uses; slope prediction's is the same (0 = off).
+// oracle's predict_and_code uses; slope prediction's is the same, -1 = off
+// (an image so small that the target is 0 bytes still predicts, as the
+// oracle does: 0 is a target like any other).
 int64_t rate_target_of(const jp2hip_recipe &rc, int w, int h) {
     return (int64_t)std::floor(rc.rate_bpp * (double)w * (double)h / 8.0);
 }
 int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h) {
-    return rc.slope_skip && rc.rate_bpp > 0.0 ? rate_target_of(rc, w, h) : 0;
+    return rc.slope_skip && rc.rate_bpp > 0.0 ? rate_target_of(rc, w, h) : -1;
 }
 // The rate loop's first budget: its header estimate (16 bytes per packet)
 // lands the usual encode under the target (C2: 8 985 521 of 9 000 000 bytes).
@@ -261,8 +263,8 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
             if (rs.safety) {
                 // slope prediction's safety net (oracle predict_and_code):
                 // planes were skipped, yet every coded byte fits -> code all
-                init.skip_target = 0;
-                if (!ctx->gpu.run_front(d_src, *lay, plan, prof, st, err, 0)) return fail(err);
+                init.skip_target = -1;
+                if (!ctx->gpu.run_front(d_src, *lay, plan, prof, st, err, -1)) return fail(err);
                 restart = true;
                 continue;
             }
@@ -359,7 +361,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         ok = ctx->gpu.t2_load(sub, tabs, err);
     }
     ok = ok && (!have || ctx->gpu.run_front(d_src, *lay, sub, prof, st, err, skip_target, &reduce, true));
-    if (skip_target > 0 && !hist_done) {  // no blocks here, or failed before the exchange
+    if (skip_target >= 0 && !hist_done) {  // no blocks here, or failed before the exchange
         std::vector<int64_t> v((size_t)kSlopeBins + 1, 0);
         if (!exchange(v, (size_t)kSlopeBins, ok)) return fail(err);
     }
@@ -416,8 +418,8 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         if (attempt == 1) {  // the prediction's safety net, decided globally (below)
             keys.clear();
             cum.clear();
-            ok = !have || ctx->gpu.run_front(d_src, *lay, sub, prof, st, err, 0, nullptr, true);
-            skip_target = 0;
+            ok = !have || ctx->gpu.run_front(d_src, *lay, sub, prof, st, err, -1, nullptr, true);
+            skip_target = -1;
             iters = 0;
         }
         if (rc.rate_bpp <= 0.0) {

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "device_common.h"
+#include "dwt_fetch.h"
 #include "gpu_encoder.h"
 #include "hip_check.h"
 #include "stage_repeat.h"
@@ -606,6 +607,9 @@ bool GpuEncoder::front_first_args(FrontJob &j, std::string &err) {
         dl.spp_strips = (plan.h + lay.rows_per_strip - 1) / lay.rows_per_strip;
         dl.ntx = plan.ntx; dl.tile_w = plan.rc.tile_w; dl.tile_h = plan.rc.tile_h; dl.row0 = plan.row0;
         dl.last_tile_w = plan.w - (plan.ntx - 1) * plan.rc.tile_w;
+        dl.src_end = source_end(lay.strip_offsets, lay.rows_per_strip, dl.spp_strips, lay.planar == 2 ? plan.nc : 1,
+                                plan.row0, plan.row0 + plan.band_h,
+                                (uint64_t)plan.w * (lay.planar == 2 ? 1 : plan.nc) * (plan.bits >> 3));
         dl.plane_w = plan.plane_w; dl.plane_h = plan.plane_h; dl.ntc = plan.ntc;
         dl.levels = plan.rc.levels; dl.reversible = plan.rc.reversible;
         dl.tc_w = (const int32_t *)tcw.ptr; dl.tc_h = (const int32_t *)tch.ptr;
@@ -684,7 +688,7 @@ bool GpuEncoder::front_quant(const FrontJob &j, std::string &err) {
     if (!ensure<T2Summary>(t2sum, 1, err)) return false;
     qa.zero[7] = (uint32_t *)&((T2Summary *)t2sum.ptr)->t1_bytes;
     qa.nzero[7] = (uint32_t)((offsetof(T2Summary, skipped) + sizeof(int32_t) - offsetof(T2Summary, t1_bytes)) / 4);
-    if (j.skip_target > 0) {
+    if (j.skip_target >= 0) {
         qa.zero[6] = (uint32_t *)hist.ptr;
         qa.nzero[6] = 2 * kSlopeBins;
     }
@@ -728,7 +732,7 @@ bool GpuEncoder::front_predict_items(const FrontJob &j, std::string &err) {
     ia.pool_cap = stream_buf.bytes;
     ia.slot_off = (uint64_t *)slotoff.ptr;
     ia.err = (int *)this->err.ptr;
-    if (skip_target > 0 && nb) {
+    if (skip_target >= 0 && nb) {
         PredictArgs pa;
         pa.nblocks = nb;
         pa.P = (const uint8_t *)P.ptr;

@@ -120,15 +120,16 @@ class GpuEncoder {
     // encode, in place; false = exchange failed (or another rank failed).
     using HistReduce = std::function<bool(std::vector<int64_t> &)>;
     // ingest, DWT, quantiser, tier-1, hulls; downloads per-block totals.
-    // skip_target > 0: rate-driven encode of skip_target bytes with slope
-    // prediction (bit-planes far below the predicted threshold not coded);
+    // skip_target >= 0: rate-driven encode of skip_target bytes with slope
+    // prediction (bit-planes far below the predicted threshold not coded;
+    // 0 bytes is a target too: a few pixels at a few bits each); -1: off;
     // reduce (tile-split only) makes the prediction global.
     // pool_worst: size the decision-stream pool for every plane of every
     // block (the tile-split path, whose ranks cannot repeat an exchange);
     // else the encode may end with kErrSlotPool in its summary's err, and
     // the caller grows the pool (pool_grow) and encodes again.
     bool run_front(const void *d_src, const jp2hip_layout &lay, const Plan &plan, bool profile,
-                   StageTimes &st, std::string &err, int64_t skip_target = 0,
+                   StageTimes &st, std::string &err, int64_t skip_target = -1,
                    const HistReduce *reduce = nullptr, bool pool_worst = false);
     // after an encode that ended with kErrSlotPool: the next run_front
     // sizes the pool for what that encode needed (+12.5 %)
