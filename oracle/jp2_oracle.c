@@ -467,13 +467,41 @@ static void mq_init(mqenc *m, uint8_t *buf /* buf[-1] must exist */) {
     m->I[CTX_UNI] = 46;
 }
 
+/* Tier-1 census (oracle_t1_census_*): plain counters of which coding states
+ * the inputs reached.  Cell layout (jp2_oracle.h, tests/oracle_lib.py):
+ *   ZC  [3 band classes][h 0..2][v 0..2][d 0..4][SPP, CUP][decision]
+ *   SC  [hc -1..1][vc -1..1][coded bit]
+ *   MR  [ctx 14..16][decision]
+ *   RL  four zeros, r = 0..3, denied by own state, denied by a neighbour
+ *       alone, denied because the stripe has fewer than 4 rows
+ *   MQ  [table index 0..46][MPS no renorm, MPS renorm + exchange, MPS renorm,
+ *       LPS + exchange, LPS, SWITCH taken]
+ *   BO  mq_byteout: after 0xFF, plain, carry, carry that makes 0xFF
+ *   FL  mq_flush: C >= tempc, C < tempc, last byte 0xFF dropped, kept
+ *   MAX decisions in one plane, decisions in one block, SPP depth */
+enum {
+    CEN_ZC = 0, CEN_SC = CEN_ZC + 3 * 3 * 3 * 5 * 2 * 2, CEN_MR = CEN_SC + 3 * 3 * 2,
+    CEN_RL = CEN_MR + 3 * 2, CEN_MQ = CEN_RL + 8, CEN_BO = CEN_MQ + 47 * 6, CEN_FL = CEN_BO + 4,
+    CEN_MAX = CEN_FL + 4, CEN_CELLS = CEN_MAX + 3
+};
+static int64_t g_cen[CEN_CELLS];
+void oracle_t1_census_reset(void) { memset(g_cen, 0, sizeof g_cen); }
+int oracle_t1_census_read(int64_t *cells, int n) {
+    if (n > CEN_CELLS) n = CEN_CELLS;
+    if (cells && n > 0) memcpy(cells, g_cen, (size_t)n * sizeof g_cen[0]);
+    return CEN_CELLS;
+}
+static void cen_max(int cell, int64_t v) { if (v > g_cen[CEN_MAX + cell]) g_cen[CEN_MAX + cell] = v; }
+
 static void mq_byteout(mqenc *m) {
     if (*m->bp == 0xFF) {
+        g_cen[CEN_BO + 0]++;
         m->bp++;
         *m->bp = (uint8_t)(m->C >> 20);
         m->C &= 0xFFFFF;
         m->CT = 7;
     } else if ((m->C & 0x8000000) == 0) {
+        g_cen[CEN_BO + 1]++;
         m->bp++;
         *m->bp = (uint8_t)(m->C >> 19);
         m->C &= 0x7FFFF;
@@ -481,12 +509,14 @@ static void mq_byteout(mqenc *m) {
     } else {
         (*m->bp)++;
         if (*m->bp == 0xFF) {
+            g_cen[CEN_BO + 3]++;
             m->C &= 0x7FFFFFF;
             m->bp++;
             *m->bp = (uint8_t)(m->C >> 20);
             m->C &= 0xFFFFF;
             m->CT = 7;
         } else {
+            g_cen[CEN_BO + 2]++;
             m->bp++;
             *m->bp = (uint8_t)(m->C >> 19);
             m->C &= 0x7FFFF;
@@ -510,20 +540,22 @@ static void mq_encode(mqenc *m, int cx, int d) {
     g_decisions++;
     int i = m->I[cx];
     uint32_t qe = QE[i];
+    int64_t *cen = g_cen + CEN_MQ + 6 * i;
     m->A -= qe;
     if (d == m->MPS[cx]) {
         if ((m->A & 0x8000) == 0) {
-            if (m->A < qe) m->A = qe;
-            else m->C += qe;
+            if (m->A < qe) { m->A = qe; cen[1]++; }
+            else { m->C += qe; cen[2]++; }
             m->I[cx] = NMPS[i];
             mq_renorm(m);
         } else {
             m->C += qe;
+            cen[0]++;
         }
     } else {
-        if (m->A < qe) m->C += qe;
-        else m->A = qe;
-        if (SWTCH[i]) m->MPS[cx] ^= 1;
+        if (m->A < qe) { m->C += qe; cen[3]++; }
+        else { m->A = qe; cen[4]++; }
+        if (SWTCH[i]) { m->MPS[cx] ^= 1; cen[5]++; }
         m->I[cx] = NLPS[i];
         mq_renorm(m);
     }
@@ -534,11 +566,13 @@ static int mq_numbytes(const mqenc *m) { return (int)(m->bp - m->start); }
 static int mq_flush(mqenc *m) {
     uint32_t tempc = m->C + m->A;
     m->C |= 0xFFFF;
+    g_cen[CEN_FL + (m->C >= tempc ? 0 : 1)]++;
     if (m->C >= tempc) m->C -= 0x8000;
     m->C <<= m->CT;
     mq_byteout(m);
     m->C <<= m->CT;
     mq_byteout(m);
+    g_cen[CEN_FL + (*m->bp == 0xFF ? 2 : 3)]++;
     if (*m->bp != 0xFF) m->bp++;
     return (int)(m->bp - m->start);
 }
@@ -611,7 +645,14 @@ static void code_sign(t1ctx *t, int x, int y) {
     if (hc == 1) { xr = 0; ctx = vc == 1 ? 13 : (vc == 0 ? 12 : 11); }
     else if (hc == 0) { xr = vc == -1; ctx = vc == 0 ? 9 : 10; }
     else { xr = 1; ctx = vc == 1 ? 11 : (vc == 0 ? 12 : 13); }
+    g_cen[CEN_SC + ((hc + 1) * 3 + (vc + 1)) * 2 + (sgn(t, x, y) ^ xr)]++;
     mq_encode(t->mq, ctx, sgn(t, x, y) ^ xr);
+}
+
+/* census: one zero-coding decision (h, v as counted, before HL's swap) */
+static void cen_zc(int band, int h, int v, int d, int cup, int bit) {
+    int cls = band == 1 ? 1 : (band == 3 ? 2 : 0);
+    g_cen[CEN_ZC + ((((cls * 3 + h) * 3 + v) * 5 + d) * 2 + cup) * 2 + bit]++;
 }
 
 int oracle_t1_encode(const int32_t *sm, int w, int h, int band, int lossless,
@@ -640,6 +681,8 @@ int oracle_t1_encode_planes(const int32_t *sm, int w, int h, int band, int lossl
     size_t fs = (size_t)(w + 2) * (h + 2);
     uint8_t *flags = (uint8_t *)calloc(3 * fs, 1);
     uint8_t *buf = (uint8_t *)malloc((size_t)cap + 1);
+    int32_t *depth = (int32_t *)calloc(fs, sizeof(int32_t)); /* census: SPP depth, this pass */
+    const int64_t dec_block0 = g_decisions;
     mqenc mq;
     mq_init(&mq, buf + 1);
     t1ctx t = {w, h, sm, flags, flags + fs, flags + 2 * fs, band, lossless, &mq};
@@ -647,23 +690,29 @@ int oracle_t1_encode_planes(const int32_t *sm, int w, int h, int band, int lossl
     if (pmin < 0) pmin = 0;
     if (pmin > P - 1) pmin = P - 1;
     for (int p = P - 1; p >= pmin; p--) {
+        const int64_t dec_plane0 = g_decisions;
         for (int pass = (p == P - 1 ? 2 : 0); pass < 3; pass++) {
             int64_t dd = 0;
+            if (pass == 0) memset(depth, 0, fs * sizeof(int32_t));
             for (int y0 = 0; y0 < h; y0 += 4) {
                 for (int x = 0; x < w; x++) {
                     int y = y0;
+                    if (pass == 2 && y0 + 4 > h) g_cen[CEN_RL + 7]++;
                     if (pass == 2 && y0 + 4 <= h) {
                         /* run-length eligibility (D.3.4) */
-                        int agg = 1;
-                        for (int yy = y0; yy < y0 + 4 && agg; yy++) {
+                        int agg = 1, own = 0;
+                        for (int yy = y0; yy < y0 + 4; yy++) {
                             int k = IDX(&t, x, yy), hh, vv, dg;
                             neigh_counts(&t, x, yy, &hh, &vv, &dg);
                             if (t.sig[k] || t.pi[k] || hh + vv + dg) agg = 0;
+                            if (t.sig[k] || t.pi[k]) own = 1;
                         }
+                        if (!agg) g_cen[CEN_RL + (own ? 5 : 6)]++;
                         if (agg) {
                             int r = -1;
                             for (int yy = y0; yy < y0 + 4; yy++)
                                 if ((mag(&t, x, yy) >> p) & 1) { r = yy - y0; break; }
+                            g_cen[CEN_RL + 1 + r]++;
                             if (r < 0) {
                                 mq_encode(&mq, CTX_RL, 0);
                                 continue;
@@ -687,9 +736,17 @@ int oracle_t1_encode_planes(const int32_t *sm, int w, int h, int band, int lossl
                         neigh_counts(&t, x, y, &hh, &vv, &dg);
                         if (pass == 0) {
                             if (t.sig[k] || !(hh + vv + dg)) continue;
+                            cen_zc(band, hh, vv, dg, 0, bit);
                             mq_encode(&mq, zc_context(band, hh, vv, dg), bit);
                             t.pi[k] = 1;
                             if (bit) {
+                                /* census: 1 + the deepest neighbour that became significant in this pass */
+                                const int w2 = w + 2;
+                                int32_t dm = 0;
+                                const int off[8] = {-w2 - 1, -w2, -w2 + 1, -1, 1, w2 - 1, w2, w2 + 1};
+                                for (int o = 0; o < 8; o++) if (depth[k + off[o]] > dm) dm = depth[k + off[o]];
+                                depth[k] = dm + 1;
+                                cen_max(2, dm + 1);
                                 dd += dist_at(v, p + 1, lossless) - dist_at(v, p, lossless);
                                 t.sig[k] = 1;
                                 code_sign(&t, x, y);
@@ -697,11 +754,13 @@ int oracle_t1_encode_planes(const int32_t *sm, int w, int h, int band, int lossl
                         } else if (pass == 1) {
                             if (!t.sig[k] || t.pi[k]) continue;
                             int ctx = t.ref[k] ? 16 : ((hh + vv + dg) ? 15 : 14);
+                            g_cen[CEN_MR + (ctx - 14) * 2 + bit]++;
                             mq_encode(&mq, ctx, bit);
                             t.ref[k] = 1;
                             dd += dist_at(v, p + 1, lossless) - dist_at(v, p, lossless);
                         } else {
                             if (t.sig[k] || t.pi[k]) continue;
+                            cen_zc(band, hh, vv, dg, 1, bit);
                             mq_encode(&mq, zc_context(band, hh, vv, dg), bit);
                             if (bit) {
                                 dd += dist_at(v, p + 1, lossless) - dist_at(v, p, lossless);
@@ -722,12 +781,14 @@ int oracle_t1_encode_planes(const int32_t *sm, int w, int h, int band, int lossl
             if (np < 100) g_pass_dec[np] = g_decisions;  /* experiments: decisions through each pass */
             np++;
             if (mq_numbytes(&mq) + 8 > cap) {
-                free(flags); free(buf);
+                free(flags); free(buf); free(depth);
                 set_err("t1: output capacity exceeded");
                 return -1;
             }
         }
+        cen_max(0, g_decisions - dec_plane0);
     }
+    cen_max(1, g_decisions - dec_block0);
     int len = mq_flush(&mq);
     rates[np - 1] = len;
     for (int i = 0; i < np; i++) {
@@ -738,6 +799,7 @@ int oracle_t1_encode_planes(const int32_t *sm, int w, int h, int band, int lossl
     *out_len = len;
     free(flags);
     free(buf);
+    free(depth);
     return np;
 }
 

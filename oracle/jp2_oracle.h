@@ -89,6 +89,15 @@ int oracle_t1_encode_planes(const int32_t *sm, int w, int h, int band, int lossl
 /* Debug: MQ decisions coded since the previous call (workload analysis). */
 int64_t oracle_debug_decisions(void);
 
+/* Tier-1 census: counters of the coding states reached since the last reset
+ * (zero-coding neighbourhoods, sign-coding configurations, refinement
+ * contexts, run-length outcomes, MQ table states and branches, byte-out and
+ * flush branches, per-block maxima); the cell layout is at g_cen in
+ * jp2_oracle.c and in tests/oracle_lib.py.  read copies min(n, cells) cells
+ * and returns the number of cells.  Counting changes no output byte. */
+void oracle_t1_census_reset(void);
+int oracle_t1_census_read(int64_t *cells, int n);
+
 void oracle_free(void *p);
 const char *oracle_last_error(void);
 

@@ -47,6 +47,9 @@ def lib():
         L.oracle_t1_encode.argtypes = [ctypes.c_void_p, c_int, c_int, c_int, c_int,
                                        ctypes.c_void_p, c_int, POINTER(c_int), ctypes.c_void_p,
                                        ctypes.c_void_p, POINTER(c_int)]
+        L.oracle_t1_census_reset.argtypes = []
+        L.oracle_t1_census_reset.restype = None
+        L.oracle_t1_census_read.argtypes = [ctypes.c_void_p, c_int]
         L.oracle_free.argtypes = [ctypes.c_void_p]
         L.oracle_last_error.restype = ctypes.c_char_p
         _L = L
@@ -131,3 +134,51 @@ def t1_encode(sm: np.ndarray, band: int, lossless: bool):
     if np_ < 0:
         raise RuntimeError(lib().oracle_last_error().decode())
     return bytes(buf[:n.value]), rates[:np_].copy(), dists[:np_].copy(), P.value
+
+
+# Tier-1 census: the cell layout of g_cen in oracle/jp2_oracle.c, as
+# (name, shape) in storage order.
+CENSUS_LAYOUT = (
+    ("zc", (3, 3, 3, 5, 2, 2)),  # band class (LL/LH, HL, HH), h, v, d, pass (SPP, CUP), decision
+    ("sc", (3, 3, 2)),           # horizontal contribution + 1, vertical + 1, coded bit
+    ("mr", (3, 2)),              # context 14, 15, 16; decision
+    ("rl", (8,)),                # RL_* below
+    ("mq", (47, 6)),             # table index; MQ_* below
+    ("byteout", (4,)),           # BO_* below
+    ("flush", (4,)),             # FL_* below
+    ("max", (3,)),               # MAX_* below
+)
+RL_ZEROS, RL_R0, RL_R1, RL_R2, RL_R3, RL_DENIED_OWN, RL_DENIED_NEIGHBOUR, RL_DENIED_SHORT = range(8)
+MQ_MPS, MQ_MPS_RENORM_XCHG, MQ_MPS_RENORM, MQ_LPS_XCHG, MQ_LPS, MQ_SWITCH = range(6)
+BO_AFTER_FF, BO_PLAIN, BO_CARRY, BO_CARRY_TO_FF = range(4)
+FL_C_GE_TEMPC, FL_C_LT_TEMPC, FL_DROP_FF, FL_KEEP = range(4)
+MAX_PLANE_DECISIONS, MAX_BLOCK_DECISIONS, MAX_SPP_DEPTH = range(3)
+CENSUS_CELLS = sum(int(np.prod(shape)) for _, shape in CENSUS_LAYOUT)
+
+
+def census_reset():
+    lib().oracle_t1_census_reset()
+
+
+def census_read() -> dict:
+    """The counters since the last census_reset(), one int64 array per
+    CENSUS_LAYOUT entry."""
+    n = lib().oracle_t1_census_read(None, 0)
+    assert n == CENSUS_CELLS, (n, CENSUS_CELLS)
+    cells = np.zeros(n, np.int64)
+    lib().oracle_t1_census_read(cells.ctypes.data, n)
+    out, at = {}, 0
+    for name, shape in CENSUS_LAYOUT:
+        k = int(np.prod(shape))
+        out[name] = cells[at:at + k].reshape(shape).copy()
+        at += k
+    return out
+
+
+def census_add(total: dict | None, c: dict) -> dict:
+    """Accumulate census `c` into `total`: counts add, maxima take the max."""
+    if total is None:
+        return {k: v.copy() for k, v in c.items()}
+    for k, v in c.items():
+        total[k] = np.maximum(total[k], v) if k == "max" else total[k] + v
+    return total
