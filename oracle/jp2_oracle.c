@@ -1091,6 +1091,19 @@ static int predict_cut(const int64_t *hist, int64_t target) {
     return k - (m ? atoi(m) : kSkipMargin);
 }
 
+/* PCRD census (oracle_pcrd_census_*): plain counters of which paths of the
+ * hull, the layer selection, the rate loop and the lossless stripes the
+ * encodes since the last reset took.  Cell names: jp2_oracle.h (PC_*),
+ * tests/oracle_lib.py.  The PC_*_MAX_* cells hold maxima, the others counts. */
+static int64_t g_pc[PC_CELLS];
+void oracle_pcrd_census_reset(void) { memset(g_pc, 0, sizeof g_pc); }
+int oracle_pcrd_census_read(int64_t *cells, int n) {
+    if (n > PC_CELLS) n = PC_CELLS;
+    if (cells && n > 0) memcpy(cells, g_pc, (size_t)n * sizeof g_pc[0]);
+    return PC_CELLS;
+}
+static void pc_max(int cell, int64_t v) { if (v > g_pc[cell]) g_pc[cell] = v; }
+
 /* T1-code every block with its predicted plane range (skip mode) */
 static int predict_and_code(encoder *E, int64_t target) {
     int64_t *hist = (int64_t *)calloc(kSlopeBins, sizeof(int64_t));
@@ -1134,6 +1147,7 @@ static int predict_and_code(encoder *E, int64_t target) {
         }
         if (ORACLE_EXP("ORACLE_SKIP_DEBUG")) fprintf(stderr, "skip pass %d: coded %lld bytes, %lld decisions so far\n", pass, (long long)total, (long long)g_decisions);
         if (pass == 0 && !(skipped && total < target)) break;
+        if (pass == 0) g_pc[PC_RATE_SAFETY_NET]++;
     }
     for (int i = 0; i < E->nall; i++) { free(E->all[i]->sm); E->all[i]->sm = NULL; }
     return 0;
@@ -1274,23 +1288,42 @@ static void build_hull(cblk *b) {
     b->hull[0] = 0;
     b->hslope[0] = 0.0;
     for (int n = 1; n <= b->npasses; n++) {
+        int pops = 0;
         for (;;) {
             int h = b->hull[b->nhull - 1];
             int64_t dD = D[n] - D[h];
             int32_t dR = R[n] - R[h];
-            if (dD <= 0) break;
-            if (dR <= 0) { b->nhull--; continue; } /* h dominated (h > 0 here) */
-            double s = (double)dD * b->weight / (double)dR;
-            if (b->nhull >= 2 && s >= b->hslope[b->nhull - 1]) { b->nhull--; continue; }
+            if (dD <= 0) { g_pc[PC_HULL_SKIP_DD]++; break; }
+            int pop = 0;
+            double s = 0.0;
+            if (dR <= 0) { pop = 1; g_pc[PC_HULL_POP_DR]++; } /* h dominated (h > 0 here) */
+            else {
+                s = (double)dD * b->weight / (double)dR;
+                if (b->nhull >= 2 && s >= b->hslope[b->nhull - 1]) {
+                    pop = 1;
+                    g_pc[s == b->hslope[b->nhull - 1] ? PC_HULL_POP_SLOPE_EQUAL : PC_HULL_POP_SLOPE]++;
+                }
+            }
+            if (pop) {
+                b->nhull--;
+                pops++;
+                g_pc[b->nhull <= 1 ? PC_HULL_POP_TO_BASE : PC_HULL_POP_READS_STACK]++;
+                continue;
+            }
             b->hull[b->nhull] = n;
             b->hslope[b->nhull] = s;
             b->nhull++;
             break;
         }
+        pc_max(PC_HULL_MAX_POPS_ONE_PASS, pops);
     }
+    pc_max(PC_HULL_MAX_POINTS, b->nhull - 1);
+    if (b->npasses == 0) g_pc[PC_HULL_BLOCK_NO_PASS]++;
+    else g_pc[b->npasses % 8 ? PC_HULL_NP_NOT_MULT8 : PC_HULL_NP_MULT8]++;
+    if (b->npasses > 88) g_pc[PC_HULL_NP_GT88]++;
 }
 
-typedef struct { uint64_t key; int32_t dr; } seg;
+typedef struct { uint64_t key; int32_t dr, blk; } seg;
 static int seg_cmp(const void *a, const void *b) {
     uint64_t x = ((const seg *)a)->key, y = ((const seg *)b)->key;
     return x < y ? 1 : (x > y ? -1 : 0);
@@ -1318,6 +1351,95 @@ static uint64_t select_threshold(const seg *S, int ns, int64_t budget, uint64_t 
     *Kc = i < ns ? S[i].key + 1 : 0;
     return K;
 }
+
+/* PCRD census of one layer's selection (Kc as select_threshold returned it):
+ * the tie group at the threshold is the first group not taken, the one the
+ * budget falls in */
+static void pc_select(const seg *S, int ns, uint64_t Kc) {
+    if (Kc == 0) { g_pc[PC_SEL_TAKES_ALL]++; return; }
+    int i = 0;
+    while (i < ns && S[i].key != Kc - 1) i++;
+    if (i == 0) g_pc[PC_SEL_TAKES_NOTHING]++;
+    int j = i, other = 0;
+    while (j < ns && S[j].key == S[i].key) { other |= S[j].blk != S[i].blk; j++; }
+    g_pc[j - i == 1 ? PC_SEL_TIE_1 : (j - i <= 64 ? PC_SEL_TIE_2_64 : PC_SEL_TIE_GT64)]++;
+    if (j - i > 1) g_pc[other ? PC_SEL_TIE_BLOCKS_DIFFER : PC_SEL_TIE_ONE_BLOCK]++;
+}
+
+/* Export of the last encode's selection (oracle_pcrd_export_*), kept only
+ * while oracle_pcrd_export_enable(1): the sorted hull segments of every
+ * rate-control group (the whole image, or each lossless flush stripe), the
+ * budget and keys of every (group, layer) of the final iteration, and every
+ * block's passes and hull. */
+typedef struct { int64_t budget; uint64_t K, Kc; int32_t group, layer; } pc_layer;
+static int g_px_on, g_px_nseg, g_px_nlayer, g_px_nblk, g_px_iters;
+static seg *g_px_seg;
+static int32_t *g_px_seg_group;
+static pc_layer *g_px_layer;
+static cblk *g_px_blk;
+void oracle_pcrd_export_enable(int on) {
+    g_px_on = on;
+    if (!on) {
+        free(g_px_seg); free(g_px_seg_group); free(g_px_layer); free(g_px_blk);
+        g_px_seg = NULL; g_px_seg_group = NULL; g_px_layer = NULL; g_px_blk = NULL;
+        g_px_nseg = g_px_nlayer = g_px_nblk = 0;
+    }
+}
+static void px_begin(const encoder *E, int nseg_max, int nlayer_max) {
+    if (!g_px_on) return;
+    oracle_pcrd_export_enable(0);
+    g_px_on = 1;
+    g_px_seg = (seg *)malloc(sizeof(seg) * (size_t)(nseg_max + 1));
+    g_px_seg_group = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nseg_max + 1));
+    g_px_layer = (pc_layer *)malloc(sizeof(pc_layer) * (size_t)(nlayer_max + 1));
+    (void)E;
+}
+static void px_end(const encoder *E) {  /* the blocks with their final layer tables */
+    if (!g_px_on) return;
+    g_px_blk = (cblk *)malloc(sizeof(cblk) * (size_t)(E->nall + 1));
+    for (int i = 0; i < E->nall; i++) {
+        g_px_blk[i] = *E->all[i];
+        g_px_blk[i].data = NULL; g_px_blk[i].sm = NULL; g_px_blk[i].pdec = NULL;
+    }
+    g_px_nblk = E->nall;
+}
+static void px_segments(const seg *S, int ns, int group) {
+    if (!g_px_on) return;
+    for (int i = 0; i < ns; i++) { g_px_seg[g_px_nseg] = S[i]; g_px_seg_group[g_px_nseg++] = group; }
+}
+static void px_layer(int group, int layer, int64_t budget, uint64_t K, uint64_t Kc) {
+    if (!g_px_on) return;
+    pc_layer r = {budget, K, Kc, group, layer};
+    g_px_layer[g_px_nlayer++] = r;
+}
+int oracle_pcrd_export_segments(uint64_t *keys, int32_t *bytes, int32_t *blocks, int32_t *groups, int n) {
+    for (int i = 0; i < n && i < g_px_nseg; i++) {
+        keys[i] = g_px_seg[i].key; bytes[i] = g_px_seg[i].dr; blocks[i] = g_px_seg[i].blk;
+        groups[i] = g_px_seg_group[i];
+    }
+    return g_px_nseg;
+}
+int oracle_pcrd_export_layers(int64_t *budgets, uint64_t *K, uint64_t *Kc, int32_t *groups, int32_t *layers, int n) {
+    for (int i = 0; i < n && i < g_px_nlayer; i++) {
+        budgets[i] = g_px_layer[i].budget; K[i] = g_px_layer[i].K; Kc[i] = g_px_layer[i].Kc;
+        groups[i] = g_px_layer[i].group; layers[i] = g_px_layer[i].layer;
+    }
+    return g_px_nlayer;
+}
+int oracle_pcrd_export_block(int i, int32_t *rates, int64_t *dd, double *weight, int32_t *hull, double *hslope,
+                             int32_t *nl, int *nhull) {
+    if (i < 0 || i >= g_px_nblk) return -1;
+    const cblk *b = &g_px_blk[i];
+    memcpy(rates, b->rates, sizeof b->rates);
+    memcpy(dd, b->dd, sizeof b->dd);
+    memcpy(hull, b->hull, sizeof(int32_t) * 101);
+    memcpy(hslope, b->hslope, sizeof b->hslope);
+    for (int l = 0; l < 32; l++) nl[l] = b->nl[l];
+    *weight = b->weight;
+    *nhull = b->nhull;
+    return b->npasses;
+}
+int oracle_pcrd_export_iterations(void) { return g_px_iters; }
 
 /* Lossless ("-rate -") layer budgets: layer l of NL keeps the passes of a
  * stripe whose slopes clear the threshold that fits lossless_budget(T, l, NL)
@@ -1830,6 +1952,7 @@ int oracle_encode(const void *pix, int w, int h, int nc, int bits, const oracle_
         for (int j = 1; j < b->nhull; j++) {
             S[k].key = slope_key(b->hslope[j]);
             S[k].dr = b->rates[b->hull[j] - 1] - (b->hull[j - 1] ? b->rates[b->hull[j - 1] - 1] : 0);
+            S[k].blk = i;
             k++;
         }
         if (b->npasses) total += b->rates[b->npasses - 1];
@@ -1844,10 +1967,15 @@ int oracle_encode(const void *pix, int w, int h, int nc, int bits, const oracle_
             if (np) ntparts++;
         }
     bytes cs = {0, 0, 0};
+    if (NL == 1) g_pc[PC_SEL_LAYERS_1]++;
+    if (NL == 32) g_pc[PC_SEL_LAYERS_32]++;
+    g_px_iters = 1;
     if (rc->rate_bpp <= 0.0) {
         /* per -flush_period stripe: its own hull segments, its own budgets */
         int *ends = (int *)malloc(sizeof(int) * (size_t)(E.nty > 0 ? E.nty : 1));
         int nst = flush_stripes(E.nty, rc->tile_h, E.h, rc->flush_period, ends);
+        px_begin(&E, ns, nst * NL);
+        g_pc[nst == 1 ? PC_LOSSLESS_STRIPES_1 : (nst == 2 ? PC_LOSSLESS_STRIPES_2 : PC_LOSSLESS_STRIPES_3_OR_MORE)]++;
         for (int l = 0; l < NL; l++) E.K[l] = 0;
         for (int st = 0, ty0 = 0; st < nst; ty0 = ends[st++]) {
             int b0 = E.tile_b0[ty0 * E.ntx], b1 = E.tile_b0[ends[st] * E.ntx];
@@ -1858,14 +1986,22 @@ int oracle_encode(const void *pix, int w, int h, int nc, int bits, const oracle_
                 for (int j = 1; j < b->nhull; j++) {
                     S[nss].key = slope_key(b->hslope[j]);
                     S[nss].dr = b->rates[b->hull[j] - 1] - (b->hull[j - 1] ? b->rates[b->hull[j - 1] - 1] : 0);
+                    S[nss].blk = i;
                     nss++;
                 }
                 if (b->npasses) stotal += b->rates[b->npasses - 1];
             }
             qsort(S, (size_t)nss, sizeof(seg), seg_cmp);
+            px_segments(S, nss, st);
+            if (stotal == 0) g_pc[PC_LOSSLESS_STRIPE_NO_BYTES]++;
+            uint64_t Kprev = 0;
             for (int l = 0; l < NL; l++) {
                 uint64_t Kc = 0;
                 uint64_t K = (l == NL - 1) ? 0 : select_threshold(S, nss, lossless_budget(stotal, l, NL), &Kc);
+                pc_select(S, nss, Kc);  /* (the last layer takes everything by rule) */
+                if (l > 0 && Kc == Kprev) g_pc[PC_SEL_SAME_AS_LAYER_BEFORE]++;
+                Kprev = Kc;
+                px_layer(st, l, lossless_budget(stotal, l, NL), K, Kc);
                 {   /* experiments: fixed normalised slope thresholds instead of budgets */
                     const char *ls = ORACLE_EXP("ORACLE_LOSSLESS_SLOPES");
                     double q[5];
@@ -1884,24 +2020,35 @@ int oracle_encode(const void *pix, int w, int h, int nc, int bits, const oracle_
     } else {
         int64_t target = (int64_t)floor(rc->rate_bpp * (double)w * (double)h / 8.0);
         int64_t budget = target - 16 * (int64_t)npackets - 16 * (int64_t)ntparts - 256;
+        px_begin(&E, ns, NL);
+        px_segments(S, ns, 0);
+        int fits = 0;
         for (int it = 0; it < 8; it++) {
-            if (budget < 0) budget = 0;
+            if (budget < 0) { g_pc[it == 0 ? PC_RATE_FIRST_BUDGET_NEGATIVE : PC_RATE_BUDGET_CLAMPED_IN_STEP]++; budget = 0; }
+            g_px_iters = it + 1;
+            g_px_nlayer = 0;
             for (int l = 0; l < NL; l++) {
                 uint64_t Kc;
                 uint64_t K = select_threshold(S, ns, budget >> (NL - 1 - l), &Kc);
+                pc_select(S, ns, Kc);
+                if (l > 0 && Kc == E.K[l - 1]) g_pc[PC_SEL_SAME_AS_LAYER_BEFORE]++;
+                px_layer(0, l, budget >> (NL - 1 - l), K, Kc);
                 E.K[l] = Kc;
                 for (int i = 0; i < E.nall; i++) E.all[i]->nl[l] = passes_for_key(E.all[i], K);
             }
             cs.n = 0;
             write_codestream(&E, &cs);
-            if ((int64_t)cs.n <= target) break;
+            if ((int64_t)cs.n <= target) { fits = 1; break; }
             if (ORACLE_EXP("ORACLE_RATE_DEBUG")) fprintf(stderr, "rate it %d budget %lld size %zu target %lld\n", it, (long long)budget, cs.n, (long long)target);
             /* exponential back-off, plus 1/16 of the overshoot and 64 bytes so
              * the second pass (headers grow with the data they describe)
              * normally lands under the target instead of needing a third */
             budget -= (((int64_t)cs.n - target) << it) + (((int64_t)cs.n - target) >> 4) + 64;
         }
+        g_pc[PC_RATE_ITERATIONS_1 + g_px_iters - 1]++;
+        g_pc[fits ? PC_RATE_STOPPED_UNDER_TARGET : PC_RATE_STOPPED_OVER_AT_8]++;
     }
+    px_end(&E);
     free(S);
     if (ORACLE_EXP("ORACLE_LAYER_DIST")) {  /* experiments: predicted distortion left after each layer */
         FILE *f = fopen(ORACLE_EXP("ORACLE_LAYER_DIST"), "a");

@@ -98,6 +98,64 @@ int64_t oracle_debug_decisions(void);
 void oracle_t1_census_reset(void);
 int oracle_t1_census_read(int64_t *cells, int n);
 
+/* PCRD census: counters of the paths the hull, the layer selection, the rate
+ * loop and the lossless stripes took since the last reset.  Counting changes
+ * no output byte.  The cells, in order (tests/oracle_lib.py names them by
+ * this list): */
+enum {
+    /* build_hull */
+    PC_HULL_SKIP_DD,            /* pass skipped: no distortion decrease over the top (dD <= 0) */
+    PC_HULL_POP_DR,             /* pop: no more bytes than the top (dR <= 0)                   */
+    PC_HULL_POP_SLOPE,          /* pop: slope above the top's (s > top)                        */
+    PC_HULL_POP_SLOPE_EQUAL,    /* pop: slope equal to the top's, to the bit (s == top)        */
+    PC_HULL_POP_TO_BASE,        /* a pop that leaves only the base point                       */
+    PC_HULL_POP_READS_STACK,    /* a pop that uncovers an earlier hull point                   */
+    PC_HULL_MAX_POPS_ONE_PASS,  /* maximum: pops caused by one pass                            */
+    PC_HULL_MAX_POINTS,         /* maximum: hull points of a block (without the base)          */
+    PC_HULL_BLOCK_NO_PASS,
+    PC_HULL_NP_MULT8,           /* blocks whose pass count (> 0) is a multiple of 8            */
+    PC_HULL_NP_NOT_MULT8,
+    PC_HULL_NP_GT88,            /* blocks with more than 88 passes                             */
+    /* one layer's selection; the tie group is the first group not taken */
+    PC_SEL_TAKES_NOTHING,
+    PC_SEL_TAKES_ALL,           /* Kc = 0                                                      */
+    PC_SEL_TIE_1, PC_SEL_TIE_2_64, PC_SEL_TIE_GT64,
+    PC_SEL_TIE_BLOCKS_DIFFER,   /* a tie group of 2 or more holds segments of different blocks */
+    PC_SEL_TIE_ONE_BLOCK,       /* ... of one block only                                       */
+    PC_SEL_SAME_AS_LAYER_BEFORE,/* the layer before has the same threshold: an empty layer     */
+    PC_SEL_LAYERS_1, PC_SEL_LAYERS_32, /* encodes with 1 and with 32 layers                    */
+    /* rate loop, per rate-driven encode */
+    PC_RATE_ITERATIONS_1,       /* 8 cells: iterations 1 .. 8                                  */
+    PC_RATE_STOPPED_UNDER_TARGET = PC_RATE_ITERATIONS_1 + 8,
+    PC_RATE_STOPPED_OVER_AT_8,
+    PC_RATE_FIRST_BUDGET_NEGATIVE,
+    PC_RATE_BUDGET_CLAMPED_IN_STEP,
+    PC_RATE_SAFETY_NET,         /* slope prediction undershot: every block coded again         */
+    /* lossless, per encode / per stripe */
+    PC_LOSSLESS_STRIPES_1, PC_LOSSLESS_STRIPES_2, PC_LOSSLESS_STRIPES_3_OR_MORE,
+    PC_LOSSLESS_STRIPE_NO_BYTES,
+    PC_CELLS
+};
+void oracle_pcrd_census_reset(void);
+int oracle_pcrd_census_read(int64_t *cells, int n);
+
+/* Export of the last encode's selection, kept only while enabled (off by
+ * default; enable(0) frees it).  Each call copies at most n entries and
+ * returns the number there are.
+ *   segments: the hull segments of every rate-control group (the image, or
+ *     each lossless flush stripe), each group sorted by key, descending;
+ *   layers: budget, threshold K and Kdu-Layer-Info key Kc of every
+ *     (group, layer) of the final rate iteration;
+ *   block i: returns its pass count (-1 past the last block) and fills
+ *     rates[100], dd[100], hull[101], hslope[101], nl[32];
+ *   iterations: rate iterations of the last encode (1 for lossless). */
+void oracle_pcrd_export_enable(int on);
+int oracle_pcrd_export_segments(uint64_t *keys, int32_t *bytes, int32_t *blocks, int32_t *groups, int n);
+int oracle_pcrd_export_layers(int64_t *budgets, uint64_t *K, uint64_t *Kc, int32_t *groups, int32_t *layers, int n);
+int oracle_pcrd_export_block(int i, int32_t *rates, int64_t *dd, double *weight, int32_t *hull, double *hslope,
+                             int32_t *nl, int *nhull);
+int oracle_pcrd_export_iterations(void);
+
 void oracle_free(void *p);
 const char *oracle_last_error(void);
 

@@ -50,6 +50,16 @@ def lib():
         L.oracle_t1_census_reset.argtypes = []
         L.oracle_t1_census_reset.restype = None
         L.oracle_t1_census_read.argtypes = [ctypes.c_void_p, c_int]
+        L.oracle_pcrd_census_reset.argtypes = []
+        L.oracle_pcrd_census_reset.restype = None
+        L.oracle_pcrd_census_read.argtypes = [ctypes.c_void_p, c_int]
+        L.oracle_pcrd_export_enable.argtypes = [c_int]
+        L.oracle_pcrd_export_enable.restype = None
+        L.oracle_pcrd_export_segments.argtypes = [ctypes.c_void_p] * 4 + [c_int]
+        L.oracle_pcrd_export_layers.argtypes = [ctypes.c_void_p] * 5 + [c_int]
+        L.oracle_pcrd_export_block.argtypes = [c_int] + [ctypes.c_void_p] * 2 + [POINTER(c_double)] + \
+            [ctypes.c_void_p] * 3 + [POINTER(c_int)]
+        L.oracle_pcrd_export_iterations.argtypes = []
         L.oracle_free.argtypes = [ctypes.c_void_p]
         L.oracle_last_error.restype = ctypes.c_char_p
         _L = L
@@ -182,3 +192,78 @@ def census_add(total: dict | None, c: dict) -> dict:
     for k, v in c.items():
         total[k] = np.maximum(total[k], v) if k == "max" else total[k] + v
     return total
+
+
+# PCRD census: the cells of oracle/jp2_oracle.h's PC_* enum, in order.  The
+# *_max_* cells hold maxima, the others counts.
+PCRD_CELLS = (
+    "hull_skip_dd", "hull_pop_dr", "hull_pop_slope", "hull_pop_slope_equal", "hull_pop_to_base", "hull_pop_reads_stack",
+    "hull_max_pops_one_pass", "hull_max_points", "hull_block_no_pass", "hull_np_mult8", "hull_np_not_mult8",
+    "hull_np_gt88",
+    "sel_takes_nothing", "sel_takes_all", "sel_tie_1", "sel_tie_2_64", "sel_tie_gt64", "sel_tie_blocks_differ",
+    "sel_tie_one_block", "sel_same_as_layer_before", "sel_layers_1", "sel_layers_32",
+    "rate_iterations_1", "rate_iterations_2", "rate_iterations_3", "rate_iterations_4", "rate_iterations_5",
+    "rate_iterations_6", "rate_iterations_7", "rate_iterations_8", "rate_stopped_under_target",
+    "rate_stopped_over_at_8", "rate_first_budget_negative", "rate_budget_clamped_in_step", "rate_safety_net",
+    "lossless_stripes_1", "lossless_stripes_2", "lossless_stripes_3_or_more", "lossless_stripe_no_bytes",
+)
+PCRD_MAX_CELLS = ("hull_max_pops_one_pass", "hull_max_points")
+
+
+def pcrd_census_reset():
+    lib().oracle_pcrd_census_reset()
+
+
+def pcrd_census_read() -> dict:
+    """The PCRD counters since the last pcrd_census_reset(), by cell name."""
+    n = lib().oracle_pcrd_census_read(None, 0)
+    assert n == len(PCRD_CELLS), (n, len(PCRD_CELLS))
+    cells = np.zeros(n, np.int64)
+    lib().oracle_pcrd_census_read(cells.ctypes.data, n)
+    return {k: int(v) for k, v in zip(PCRD_CELLS, cells)}
+
+
+def pcrd_census_add(total: dict | None, c: dict) -> dict:
+    if total is None:
+        return dict(c)
+    for k, v in c.items():
+        total[k] = max(total[k], v) if k in PCRD_MAX_CELLS else total[k] + v
+    return total
+
+
+def pcrd_export_enable(on: bool):
+    lib().oracle_pcrd_export_enable(1 if on else 0)
+
+
+def pcrd_export() -> dict:
+    """The last encode's selection (oracle_pcrd_export_*): `segments` (key,
+    bytes, block, group) sorted by key, descending, within each group;
+    `layers` (group, layer, budget, K, Kc) of the final iteration; `blocks`
+    (rates, dd, weight, hull, hslope, nl) per block; `iterations`."""
+    L = lib()
+    n = L.oracle_pcrd_export_segments(None, None, None, None, 0)
+    keys, nbytes = np.zeros(n, np.uint64), np.zeros(n, np.int32)
+    blocks, groups = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    L.oracle_pcrd_export_segments(keys.ctypes.data, nbytes.ctypes.data, blocks.ctypes.data, groups.ctypes.data, n)
+    m = L.oracle_pcrd_export_layers(None, None, None, None, None, 0)
+    bud, K, Kc = np.zeros(m, np.int64), np.zeros(m, np.uint64), np.zeros(m, np.uint64)
+    lg, ll = np.zeros(m, np.int32), np.zeros(m, np.int32)
+    L.oracle_pcrd_export_layers(bud.ctypes.data, K.ctypes.data, Kc.ctypes.data, lg.ctypes.data, ll.ctypes.data, m)
+    out_blocks = []
+    rates, dd = np.zeros(100, np.int32), np.zeros(100, np.int64)
+    hull, hslope, nl = np.zeros(101, np.int32), np.zeros(101, np.float64), np.zeros(32, np.int32)
+    w, nh = c_double(), c_int()
+    i = 0
+    while True:
+        np_ = L.oracle_pcrd_export_block(i, rates.ctypes.data, dd.ctypes.data, byref(w), hull.ctypes.data,
+                                         hslope.ctypes.data, nl.ctypes.data, byref(nh))
+        if np_ < 0:
+            break
+        out_blocks.append(dict(rates=[int(x) for x in rates[:np_]], dd=[int(x) for x in dd[:np_]], weight=w.value,
+                               hull=[int(x) for x in hull[:nh.value]], hslope=[float(x) for x in hslope[:nh.value]],
+                               nl=[int(x) for x in nl]))
+        i += 1
+    return dict(segments=[(int(k), int(b), int(bl), int(g)) for k, b, bl, g in zip(keys, nbytes, blocks, groups)],
+                layers=[dict(group=int(g), layer=int(l), budget=int(b), K=int(k), Kc=int(kc))
+                        for g, l, b, k, kc in zip(lg, ll, bud, K, Kc)],
+                blocks=out_blocks, iterations=int(L.oracle_pcrd_export_iterations()))
