@@ -63,7 +63,16 @@ typedef struct jp2hip_config {
 typedef struct jp2hip_recipe {
     int32_t levels;          /* Clevels=6                                      */
     int32_t layers;          /* Clayers=6                                      */
-    int32_t tile_w, tile_h;  /* Stiles={512,512}; at most 65535 tiles          */
+    int32_t tile_w, tile_h;  /* Stiles={512,512}: multiples of 2^levels, each  */
+                             /* at most 32768 (so a tile-component has at most */
+                             /* 2^30 samples), at most 65535 tiles.  Both 0:   */
+                             /* no Stiles, one tile for the whole image -- the */
+                             /* smallest multiples of 2^levels not below width */
+                             /* and height, written to SIZ as they are; one of */
+                             /* them 0, or a negative one, is refused.  A tile */
+                             /* is also refused (the message names the field)  */
+                             /* where its packets outgrow a tile-part header:  */
+                             /* 256 PLT segments (Zplt), 2^32 - 1 bytes (Psot) */
     int32_t cblk_w_log2;     /* Cblk={64,64}                                   */
     int32_t cblk_h_log2;
     int32_t nprecincts;      /* Cprecincts={256,256},{256,256},{128,128}:     */
@@ -353,7 +362,9 @@ typedef struct jp2hip_split {
 
 /* Image rows [*row0, *row1) whose tiles rank `rank` encodes: whole
  * -flush_period stripes of tile rows (recipe.flush_period), so every rank's
- * tile-parts are one contiguous run of the file. */
+ * tile-parts are one contiguous run of the file.  tile_h = 0 is the untiled
+ * recipe (tile_w = tile_h = 0): one tile row, which is all rank 0's -- the
+ * other ranks get the empty band [height, height). */
 void jp2hip_split_rows(int32_t height, int32_t tile_h, int32_t flush_period, int32_t rank, int32_t world,
                        int32_t *row0, int32_t *row1);
 
@@ -382,8 +393,10 @@ int jp2hip_encode_device_split(jp2hip_ctx *ctx, const void *d_src, size_t src_le
  * at its offset of the output file; the ranks' exchanges are summed on the
  * host (no caller callback, no RCCL needed in-process).  The file is
  * byte-identical to the single-GPU encode.  Smaller images take the
- * single-GPU path.  n = 0 removes the peers.  Not to be called while ctx is
- * encoding.  Returns 0 or < 0. */
+ * single-GPU path.  The split divides tile rows: an untiled image (tile_w =
+ * tile_h = 0) or any image of one tile row gains nothing from it -- one rank
+ * encodes everything, the others only join the exchanges.  n = 0 removes the
+ * peers.  Not to be called while ctx is encoding.  Returns 0 or < 0. */
 int jp2hip_split_peers(jp2hip_ctx *ctx, const int32_t *ordinals, int32_t n, int64_t min_pixels);
 
 /* Width x height of a TIFF file from its header (the file is mapped, not
@@ -405,7 +418,8 @@ int jp2hip_split_thresholds(const uint64_t *keys, const int64_t *cum, int64_t ns
  * exported for tests.  Entry s names the s-th packet as p * layers + l: layer
  * l of the tile's p-th precinct counted in (resolution, precinct row, precinct
  * column, component) order, the order the packets are stored in (so RPCL
- * gives 0, 1, 2, ...).  Returns the tile's packet count and writes the first
+ * gives 0, 1, 2, ...).  tile_w = tile_h = 0 means what it means to an encode:
+ * one tile.  Returns the tile's packet count and writes the first
  * min(count, cap) entries to seq (which may be NULL when cap is 0), or < 0
  * with jp2hip_last_error() for a recipe or geometry the encodes refuse. */
 int64_t jp2hip_packet_sequence(int32_t width, int32_t height, int32_t components, int32_t bits,

@@ -325,7 +325,10 @@ int64_t jp2hip_packet_sequence(int32_t width, int32_t height, int32_t components
     // the function its tier-2 tables take the order from
     jp2hip::Plan plan;
     std::string err;
-    if (!jp2hip::build_plan(plan, *recipe, width, height, components, bits, err)) return fail(err);
+    jp2hip_recipe rc = *recipe;
+    if (!jp2hip::resolve_tiles(rc, width, height, err) ||
+        !jp2hip::build_plan(plan, rc, width, height, components, bits, err))
+        return fail(err);
     if (tile < 0 || tile >= plan.ntx * plan.nty) return fail("tile index outside the image's tiles");
     std::vector<uint32_t> s;
     jp2hip::packet_sequence(plan, tile, s);

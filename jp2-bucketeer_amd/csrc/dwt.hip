@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "device_common.h"
+#include "dwt_chunk.h"
 #include "dwt_fetch.h"
 #include "gpu_encoder.h"
 
@@ -53,7 +54,8 @@ namespace jp2hip {
 constexpr int kDwtThreads = 256;
 constexpr int kDwtHalo = 4;           // >= lifting steps (9/7: 4, 5/3: 2)
 constexpr int kDwtLdsWords = 16384;   // 64 KiB: band workgroups for rows <= 1024, tail
-constexpr int kDwtLdsWordsWide = 32768;  // 128 KiB: band workgroups for rows of 2048 / 4096 (8 rows)
+constexpr int kDwtLdsWordsWide = 32768;  // 128 KiB: what the wide instances opt in to (level 1's routes compare with it)
+static_assert(kDwtHalo == kDwtChunkHalo, "one halo, rows and columns");
 
 // One lifting step over the LDS rows [ya, yb) of a column set (vertical) or
 // over one row (horizontal).  Sample i of parity `par` is updated from
@@ -412,24 +414,29 @@ __device__ __forceinline__ void hlift_write(int32_t *lds, int W, int ld, bool q1
 // the 4-step footprint: the 16 kept samples are exact, as in lift_regs),
 // scaled and written de-interleaved as 8 low + 8 high words (two 16-byte
 // stores each when the row is aligned).  Rows as in hlift_write.
+// A column chunk (dwt_chunk.h; ALIGNED = false) lifts the `cseg` segments
+// from the row's segment `seg0` on: the staged rows then begin at the chunk's
+// first window sample, W stays the whole row's width, so the row ends and
+// the output places are the row's.
 template <bool REV, int NROWS, bool ALIGNED, int NT = kDwtThreads, bool SKEW = false, typename RowFn>
 __device__ __forceinline__ void hlift_seg(const int32_t *lds, int W, int ld, bool q16, RowFn rows,
-                                          int nrows = NROWS) {
-    const int nseg = (W + 15) >> 4;
+                                          int nrows = NROWS, int seg0 = 0, int cseg = 0) {
+    const int nseg = cseg ? cseg : (W + 15) >> 4;
     const int nlh = (W + 1) / 2;
     for (int it = threadIdx.x; it < nrows * nseg; it += NT) {
-        const int r = it / nseg, k = it - r * nseg;
+        const int r = it / nseg, kl = it - r * nseg;
+        const int k = seg0 + kl;      // the row's segment; kl: its place in the staged rows
         const int x0 = (k << 4) - 4;  // window: samples x0 .. x0+23 (even start)
         int32_t v[24];
         if (SKEW) {  // segment k's samples at word 20 k: the halos are the neighbours' edges
-            const int32_t *rb = lds + kPadLs + r * ld + 20 * k;
+            const int32_t *rb = lds + kPadLs + r * ld + 20 * kl;
 #pragma unroll
             for (int q = 0; q < 6; q++) {
                 const int4 t = *(const int4 *)(rb + (q == 0 ? -8 : (q == 5 ? 20 : 4 * (q - 1))));
                 v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
             }
         } else {
-            const int4 *src = (const int4 *)(lds + kPadL + r * ld + x0);
+            const int4 *src = (const int4 *)(lds + kPadL + r * ld + (kl << 4) - 4);
 #pragma unroll
             for (int q = 0; q < 6; q++) {
                 const int4 t = src[q];
@@ -528,7 +535,11 @@ __device__ __forceinline__ void hlift_seg(const int32_t *lds, int W, int ld, boo
     }
 }
 
-template <bool REV, bool INGEST, int RB, int NT = kDwtThreads>
+// CHUNK: a level whose rows do not fit in LDS; workgroup (band, tc, k) owns
+// the band's rows x column chunk k of kBandChunkW kept columns (dwt_chunk.h):
+// it stages the chunk and its halo columns, lifts the chunk's segments and
+// writes their outputs to the row's places.
+template <bool REV, bool INGEST, int RB, int NT = kDwtThreads, bool CHUNK = false>
 __global__ void __launch_bounds__(NT) k_dwt_band(DwtBandArgs a) {
     extern __shared__ int32_t lds[];
     constexpr int NR = RB + 2 * kDwtHalo;
@@ -541,9 +552,16 @@ __global__ void __launch_bounds__(NT) k_dwt_band(DwtBandArgs a) {
     const int nkeep = min(RB, H - r0);
     const int y0 = r0 - kDwtHalo;
     const int tid = threadIdx.x;
-    const int ld = lds_row_stride(W);
+    // staged columns [xa, xb); column x of staged row i at lds[kPadL + i * ld + x - xc]
+    int xa = 0, xb = W, xc = 0, ld = lds_row_stride(W);
+    if constexpr (CHUNK) {
+        if ((int)blockIdx.z >= dwt_chunk_count(W, kBandChunkW)) return;
+        const DwtChunk ch = dwt_chunk(W, kBandChunkW, blockIdx.z);
+        xa = ch.s0; xb = ch.s1; xc = ch.c0;
+        ld = lds_row_stride(dwt_chunk_staged(kBandChunkW));
+    }
     // ---- vertical: one column per thread, in registers ----
-    for (int x = tid; x < W; x += NT) {
+    for (int x = xa + tid; x < xb; x += NT) {
         int32_t v[NR];
         // every row load issues before any is used: rows outside the band
         // read a clamped (valid) row (a load under a per-row branch was
@@ -574,13 +592,14 @@ __global__ void __launch_bounds__(NT) k_dwt_band(DwtBandArgs a) {
         }
         int ldv = ld, nkv = nkeep;
         if constexpr (!INGEST) asm volatile("" : "+v"(ldv), "+v"(nkv));
+        const int xl = x - xc;
         if (nkeep == RB) {  // every band but a region's last
 #pragma unroll
-            for (int i = 0; i < RB; i++) lds[kPadL + i * ldv + x] = v[kDwtHalo + i];
+            for (int i = 0; i < RB; i++) lds[kPadL + i * ldv + xl] = v[kDwtHalo + i];
         } else {
 #pragma unroll
             for (int i = 0; i < RB; i++)
-                if (i < nkv) lds[kPadL + i * ldv + x] = v[kDwtHalo + i];
+                if (i < nkv) lds[kPadL + i * ldv + xl] = v[kDwtHalo + i];
         }
     }
     __syncthreads();
@@ -598,8 +617,13 @@ __global__ void __launch_bounds__(NT) k_dwt_band(DwtBandArgs a) {
         qrow_bands(o, ql, !ylo);
         return true;
     };
-    if (W > 1 && (W & 15) == 0) hlift_seg<REV, RB, true, NT>(lds, W, ld, q16, rows);
-    else hlift_seg<REV, RB, false, NT>(lds, W, ld, q16, rows);
+    if constexpr (CHUNK) {
+        const DwtChunk ch = dwt_chunk(W, kBandChunkW, blockIdx.z);
+        hlift_seg<REV, RB, false, NT>(lds, W, ld, q16, rows, RB, ch.c0 >> 4, (ch.c1 - ch.c0 + 15) >> 4);
+    } else {
+        if (W > 1 && (W & 15) == 0) hlift_seg<REV, RB, true, NT>(lds, W, ld, q16, rows);
+        else hlift_seg<REV, RB, false, NT>(lds, W, ld, q16, rows);
+    }
 }
 
 // Level 1 with ingest, every component of a tile at once: a workgroup owns
@@ -611,7 +635,12 @@ __global__ void __launch_bounds__(NT) k_dwt_band(DwtBandArgs a) {
 // de-interleaved write puts HL/LH/HH in their final Mallat place and LL in the
 // next level's scratch.  Same expressions as band_load / lift_regs /
 // k_dwt_band (bit-exact with the oracle).
-template <bool REV, int NC, int RB>
+// CHUNK: a tile whose rows do not fit in LDS; workgroup (band, tile, k) owns
+// the band's rows x column chunk k of kL1ChunkW kept columns (dwt_chunk.h),
+// every component: a pixel is still read once per workgroup, only the halo
+// columns by two of them.  The horizontal lifting is then hlift_seg's over
+// the chunk's segments (hlift_write's barrier-stepped passes lift whole rows).
+template <bool REV, int NC, int RB, bool CHUNK = false>
 __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
     extern __shared__ int32_t lds[];
     constexpr int NR = RB + 2 * kDwtHalo;
@@ -623,7 +652,14 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
     const int nkeep = min(RB, H - r0);
     const int y0 = r0 - kDwtHalo;
     const int tid = threadIdx.x;
-    const int ld = lds_row_stride(W);
+    // staged columns [xa, xb); column x of staged row i at lds[kPadL + i * ld + x - xc]
+    int xa = 0, xb = W, xc = 0, ld = lds_row_stride(W);
+    if constexpr (CHUNK) {
+        if ((int)blockIdx.z >= dwt_chunk_count(W, kL1ChunkW)) return;
+        const DwtChunk ch = dwt_chunk(W, kL1ChunkW, blockIdx.z);
+        xa = ch.s0; xb = ch.s1; xc = ch.c0;
+        ld = lds_row_stride(dwt_chunk_staged(kL1ChunkW));
+    }
     const int32_t off = 1 << (a.bits - 1);
     const size_t row_bytes = (size_t)a.img_w * (a.planar == 2 ? 1 : NC) * (a.bits >> 3);
     const int gx0 = (t % a.ntx) * a.tile_w, gy0 = a.row0 + (t / a.ntx) * a.tile_h;
@@ -642,7 +678,7 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
             rowoff[c][i] = a.strip_off[a.planar == 2 ? (size_t)c * a.spp_strips + strip : (size_t)strip] + ly;
     }
     const int bps = a.bits >> 3;
-    for (int x = tid; x < W; x += kDwtThreads) {
+    for (int x = xa + tid; x < xb; x += kDwtThreads) {
         int32_t v[NC][NR];
         const int gx = gx0 + x;
         const size_t xo = a.planar == 2 ? (size_t)gx * bps : (size_t)gx * NC * bps;
@@ -692,7 +728,7 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
             }
 #pragma unroll
             for (int i = 0; i < RB; i++)
-                if (i < nkeep) lds[kPadL + (c * RB + i) * ld + x] = v[c][kDwtHalo + i];
+                if (i < nkeep) lds[kPadL + (c * RB + i) * ld + x - xc] = v[c][kDwtHalo + i];
         }
     }
     __syncthreads();
@@ -700,7 +736,7 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
     const int nlv = (H + 1) / 2;
     const bool q16 = a.qt.q16 != 0;
     const QLevel ql = qlevel(a.qt, a.level);
-    hlift_write<REV, NC * RB>(lds, W, ld, q16, [&](int r, QRow &o) -> bool {
+    auto rows = [&](int r, QRow &o) -> bool {
         const int c = r / RB, k = r - c * RB;
         if (k >= nkeep) return false;
         const int tc = tc0 + c, y = r0 + k;
@@ -709,7 +745,13 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
         o.ll = (ylo && a.ll) ? (int32_t *)a.ll + (size_t)tc * a.ll_tc + (size_t)(y >> 1) * a.ll_stride : nullptr;
         qrow_bands(o, ql, !ylo);
         return true;
-    });
+    };
+    if constexpr (CHUNK) {
+        const DwtChunk ch = dwt_chunk(W, kL1ChunkW, blockIdx.z);
+        hlift_seg<REV, NC * RB, false>(lds, W, ld, q16, rows, NC * RB, ch.c0 >> 4, (ch.c1 - ch.c0 + 15) >> 4);
+    } else {
+        hlift_write<REV, NC * RB>(lds, W, ld, q16, rows);
+    }
 }
 
 // Level 1 with ingest, streaming: a workgroup owns a band of kStreamBand
@@ -1203,6 +1245,38 @@ static void launch_band_rb(int maxW, dim3 g, size_t lds, hipStream_t st, const D
         launch_band<REV, INGEST, kBandRb, kDwtThreads>(g, lds, st, a);
 }
 
+// the chunked instances (dwt_chunk.h): the LDS of a chunk's staged rows,
+// whatever the level's width; grid z = chunks of the widest tile-component
+constexpr size_t band_chunk_lds(int rows, int C) {
+    return ((size_t)rows * lds_row_stride(dwt_chunk_staged(C)) + kPadL + kPadR) * 4;
+}
+template <bool REV>
+static void launch_band_chunk(dim3 g, hipStream_t st, const DwtBandArgs &a) {
+    constexpr size_t lds = band_chunk_lds(kBandRb, kBandChunkW);
+    static_assert(lds <= (size_t)kDwtLdsWords * 4, "a chunked band fits the default 64 KiB of dynamic LDS");
+    hipLaunchKernelGGL((k_dwt_band<REV, false, kBandRb, kDwtThreads, true>), g, dim3(kDwtThreads), lds, st, a);
+}
+constexpr int kRb1 = 8;  // k_dwt_l1's kept rows per workgroup
+template <bool REV, int NC>
+static void launch_l1_chunk_nc(dim3 g, hipStream_t st, const DwtBandArgs &a) {
+    constexpr size_t lds = band_chunk_lds(NC * kRb1, kL1ChunkW);
+    static_assert(lds <= (size_t)kDwtLdsWordsWide * 4, "a chunked level 1 fits the 128 KiB the instance opts in to");
+    static bool wide = false;
+    if (lds > (size_t)kDwtLdsWords * 4 && !wide) {
+        (void)hipFuncSetAttribute((const void *)k_dwt_l1<REV, NC, kRb1, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kDwtLdsWordsWide * 4);
+        wide = true;
+    }
+    hipLaunchKernelGGL((k_dwt_l1<REV, NC, kRb1, true>), g, dim3(kDwtThreads), lds, st, a);
+}
+template <bool REV>
+static void launch_l1_chunk(int nc, dim3 g, hipStream_t st, const DwtBandArgs &a) {
+    if (nc == 1) launch_l1_chunk_nc<REV, 1>(g, st, a);
+    else if (nc == 2) launch_l1_chunk_nc<REV, 2>(g, st, a);
+    else if (nc == 3) launch_l1_chunk_nc<REV, 3>(g, st, a);
+    else launch_l1_chunk_nc<REV, 4>(g, st, a);
+}
+
 template <bool REV, int NC>
 static void launch_l1_nc(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
     static bool wide = false;
@@ -1268,8 +1342,21 @@ static void launch_l1(int nc, dim3 g, size_t lds, hipStream_t st, const DwtBandA
     else launch_l1_nc<REV, 4>(g, lds, st, a);
 }
 
-// Ingest + all DWT levels on `st`.  Returns false on a launch error.
-bool launch_dwt(const DwtLaunch &p, hipStream_t st) {
+// What a gfx950 workgroup can be given: 160 KiB of LDS.  A level whose band
+// of whole rows asks for no more keeps the whole-row kernels (the runtime
+// grants a launch up to the device's limit); a wider one goes to the chunked
+// instances, whose LDS does not depend on the width (static_asserts above).
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+static bool grid_ok(dim3 g) { return g.x >= 1 && g.y >= 1 && g.y <= 65535 && g.z >= 1 && g.z <= 65535; }
+static bool refuse(const char **why, const char *msg) {
+    if (why) *why = msg;
+    return false;
+}
+
+// Ingest + all DWT levels on `st`.  Returns false on a launch error, or
+// (*why set) without launching where a launch could not be valid.
+bool launch_dwt(const DwtLaunch &p, hipStream_t st, const char **why) {
+    if (why) *why = nullptr;
     DwtBandArgs a;
     a.tif = (const uint8_t *)p.tif;
     a.strip_off = p.strip_off;
@@ -1319,7 +1406,6 @@ bool launch_dwt(const DwtLaunch &p, hipStream_t st) {
         dim3 g((maxH + R - 1) / R, p.ntc);
         // level 1: every component of a tile in one workgroup when its rows
         // fit in LDS (each TIFF pixel read once)
-        constexpr int kRb1 = 8;
         const size_t lds1 = ((size_t)p.nc * kRb1 * lds_row_stride(maxW) + kPadL + kPadR) * 4;
         const int cpt = maxW <= kDwtThreads ? 1 : (maxW <= 2 * kDwtThreads ? 2 : 4);
         if (lv == 1 && lds1 <= (size_t)kDwtLdsWordsWide * 4 && maxW <= 4 * kDwtThreads) {
@@ -1336,6 +1422,20 @@ bool launch_dwt(const DwtLaunch &p, hipStream_t st) {
             dim3 g1((maxH + kRb1 - 1) / kRb1, p.ntc / p.nc);
             if (p.reversible) launch_l1<true>(p.nc, g1, lds1, st, a);
             else launch_l1<false>(p.nc, g1, lds1, st, a);
+        } else if (lds > kLdsPerWorkgroup) {
+            // whole rows of this level do not fit in a workgroup's LDS: column
+            // chunks (level 1: every component of a tile per workgroup)
+            if (lv == 1) {
+                dim3 gc((maxH + kRb1 - 1) / kRb1, p.ntc / p.nc, dwt_chunk_count(maxW, kL1ChunkW));
+                if (!grid_ok(gc)) return refuse(why, "DWT: the tile needs more workgroups than a launch takes");
+                if (p.reversible) launch_l1_chunk<true>(p.nc, gc, st, a);
+                else launch_l1_chunk<false>(p.nc, gc, st, a);
+            } else {
+                dim3 gc(g.x, g.y, dwt_chunk_count(maxW, kBandChunkW));
+                if (!grid_ok(gc)) return refuse(why, "DWT: the tile needs more workgroups than a launch takes");
+                if (p.reversible) launch_band_chunk<true>(gc, st, a);
+                else launch_band_chunk<false>(gc, st, a);
+            }
         } else if (lv == 1) {
             if (p.reversible) launch_band_rb<true, true>(maxW, g, lds, st, a);
             else launch_band_rb<false, true>(maxW, g, lds, st, a);

@@ -87,6 +87,8 @@ int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conv
     if (world > 1 && !sp->allreduce_sum) return fail("split: world > 1 needs an allreduce_sum callback");
     rc = recipe_of(recipe, conversion);
     if (!lay || !d_src) return fail("null source or layout");
+    std::string terr;  // tile_w = tile_h = 0: one tile for this image
+    if (!resolve_tiles(rc, lay->width, lay->height, terr)) return fail(terr);
     meta = source_meta(*lay);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
     ctx->gpu.take_waits();     // count this encode's host waits (stats)
     ctx->gpu.begin_encode();
@@ -326,7 +328,12 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     encoded_format(*lay, enc_nc, enc_bits);
     if (!build_plan(full, rc, lay->width, lay->height, enc_nc, enc_bits, err)) return fail(err);
     int tr0, tr1;
-    split_tile_rows(full.nty, rc.tile_h, full.h, rc.flush_period, rank, world, tr0, tr1);
+    if (untiled(recipe)) {  // one tile row, all of it rank 0's (jp2hip_split_rows with tile_h = 0)
+        tr0 = rank ? 1 : 0;
+        tr1 = 1;
+    } else {
+        split_tile_rows(full.nty, rc.tile_h, full.h, rc.flush_period, rank, world, tr0, tr1);
+    }
     Plan sub;
     make_subplan(full, tr0, tr1, sub);
     const bool have = sub.ntc > 0;

@@ -627,9 +627,10 @@ bool GpuEncoder::front_ingest_dwt(const FrontJob &j, std::string &err) {
         HIPCHECK(hipGetLastError());
     } else {
         bool dwt_ok = true;
-        REPEAT_IF(1) dwt_ok = dwt_ok && launch_dwt(j.dl, stream);
+        const char *why = nullptr;
+        REPEAT_IF(1) dwt_ok = dwt_ok && launch_dwt(j.dl, stream, &why);
         if (!dwt_ok) {
-            err = std::string("DWT launch failed: ") + hipGetErrorString(hipGetLastError());
+            err = why ? std::string(why) : std::string("DWT launch failed: ") + hipGetErrorString(hipGetLastError());
             return false;
         }
     }

@@ -127,6 +127,15 @@ struct Plan {
 
 bool build_plan(Plan &plan, const jp2hip_recipe &rc, int w, int h, int nc, int bits,
                 std::string &err);
+// The largest tile side: BlockDesc::x0 / y0 are 16 bits, and a
+// tile-component plane of at most 2^30 elements is indexed with an int.
+constexpr int kMaxTileSide = 32768;
+// What rc.tile_w / tile_h mean for a w x h image, resolved before build_plan
+// by everything that takes a caller's recipe: 0 and 0 become one tile for the
+// whole image, the smallest multiples of 2^levels not below w and h (written
+// to SIZ as they are); one of them 0, or a negative one, is refused.
+bool resolve_tiles(jp2hip_recipe &rc, int w, int h, std::string &err);
+inline bool untiled(const jp2hip_recipe *rc) { return rc && rc->tile_w == 0 && rc->tile_h == 0; }
 
 int prec_log2(const jp2hip_recipe &rc, int r, bool vertical);
 

@@ -181,6 +181,24 @@ QuantTab quant_tab(const jp2hip_recipe &rc, int bits) {
     return t;
 }
 
+bool resolve_tiles(jp2hip_recipe &rc, int w, int h, std::string &err) {
+    if (rc.tile_w != 0 || rc.tile_h != 0) {
+        if (rc.tile_w > 0 && rc.tile_h > 0) return true;  // stated (build_plan checks the rest)
+        err = "tile size: tile_w and tile_h must both be above 0, or both 0 (one tile for the whole image)";
+        return false;
+    }
+    if (w <= 0 || h <= 0 || rc.levels < 0 || rc.levels > kMaxLevels) return true;  // build_plan refuses these
+    const int64_t m = (int64_t)1 << rc.levels;
+    const int64_t tw = cdiv(w, m) * m, th = cdiv(h, m) * m;
+    if (tw > kMaxTileSide || th > kMaxTileSide) {
+        err = "tile size: one tile for this image would be more than 32768 on a side";
+        return false;
+    }
+    rc.tile_w = (int32_t)tw;
+    rc.tile_h = (int32_t)th;
+    return true;
+}
+
 bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits,
                 std::string &err) {
     if (w <= 0 || h <= 0 || nc < 1 || nc > 4 || (bits != 8 && bits != 16)) {
@@ -203,9 +221,12 @@ bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits
         err = "levels must be 0..12 and layers 1..32";
         return false;
     }
+    // at most 32768 on a side: a code-block's place in its tile-component
+    // (BlockDesc::x0, y0) is 16 bits, and the plane then has at most 2^30
+    // elements, so an index inside it fits an int
     if (rc.tile_w <= 0 || rc.tile_h <= 0 || (rc.tile_w % (1 << rc.levels)) ||
-        (rc.tile_h % (1 << rc.levels)) || rc.tile_w > 4096 || rc.tile_h > 4096) {
-        err = "tile size must be a multiple of 2^levels and <= 4096";
+        (rc.tile_h % (1 << rc.levels)) || rc.tile_w > kMaxTileSide || rc.tile_h > kMaxTileSide) {
+        err = "tile size must be a multiple of 2^levels and <= 32768 (tile_w = tile_h = 0: one tile for the image)";
         return false;
     }
     if (rc.cblk_w_log2 < 2 || rc.cblk_w_log2 > 6 || rc.cblk_h_log2 < 2 || rc.cblk_h_log2 > 6) {
@@ -353,10 +374,40 @@ bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits
                     }
                 }
             }
+            int64_t tile_packets = 0, part_packets = 0;  // of the tile; of its largest tile-part
             for (int r = 0; r <= L; r++) {
                 int np = T.tc[0].res[r].npx * T.tc[0].res[r].npy;
                 P.npackets += (int64_t)np * nc * rc.layers;
+                tile_packets += (int64_t)np * nc * rc.layers;
+                part_packets = std::max(part_packets, (int64_t)np * nc * rc.layers);
                 if (np) P.ntileparts++;
+            }
+            if (!rc.tparts_r) part_packets = tile_packets;
+            // What a large tile can outgrow in its tile-part headers.  Nsop is
+            // the packet's number in its tile modulo 65536 (A.8.1), so it only
+            // has to fit the tables' int32.
+            if (tile_packets > INT32_MAX) {
+                err = "a tile has more than 2^31 - 1 packets (smaller tiles, larger precincts or fewer layers)";
+                return false;
+            }
+            // Zplt is 8 bits: at most 256 PLT segments of 65532 length bytes
+            // in a tile-part header, a packet's length taking at most 5
+            if (rc.plt && part_packets * 5 > (int64_t)256 * 65532) {
+                err = "a tile-part has more packets than 256 PLT segments hold (Zplt is 8 bits): smaller tiles, "
+                      "larger precincts, fewer layers, or plt = 0";
+                return false;
+            }
+            // Psot is 32 bits: the tile's tile-parts stay below 2^32 bytes if
+            // everything tier-1 may emit for it, its packet headers (a length
+            // and pass count per block and layer, 8 bytes at the most; SOP,
+            // EPH and the empty-packet bit, 9) and its PLT lengths do
+            uint64_t tile_cap = 0;
+            for (size_t b = (size_t)P.tile_b0.back(); b < P.blocks.size(); b++)
+                tile_cap += P.blocks[b].out_cap + (uint64_t)8 * rc.layers;
+            tile_cap += (uint64_t)tile_packets * (9 + 5) + 14 * (uint64_t)(L + 1) + (uint64_t)5 * 256 * (L + 1);
+            if (tile_cap > 0xFFFFFFFFull) {
+                err = "a tile's code-blocks could fill a tile-part beyond 2^32 - 1 bytes (Psot is 32 bits): smaller tiles";
+                return false;
             }
         }
     }

@@ -42,6 +42,12 @@ extern "C" {
 void jp2hip_split_rows(int32_t height, int32_t tile_h, int32_t flush_period, int32_t rank, int32_t world,
                        int32_t *row0, int32_t *row1) {
     int tr0 = 0, tr1 = 0;
+    if (tile_h == 0) {  // untiled: one tile row, which the tile-split cannot divide; all of it is rank 0's
+        const bool valid = height > 0 && world > 0 && rank >= 0 && rank < world;
+        if (row0) *row0 = valid && rank ? height : 0;
+        if (row1) *row1 = valid ? height : 0;
+        return;
+    }
     if (tile_h > 0 && height > 0 && world > 0 && rank >= 0 && rank < world)
         jp2hip::split_tile_rows((height + tile_h - 1) / tile_h, tile_h, height, flush_period, rank, world, tr0, tr1);
     if (row0) *row0 = (int32_t)std::min<int64_t>(height, (int64_t)tr0 * tile_h);

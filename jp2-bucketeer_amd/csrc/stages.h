@@ -121,7 +121,8 @@ struct DwtLaunch {
     void *coef, *scratch0, *scratch1;  // scratch: ntc * ceil(plane_w/2) * ceil(plane_h/2) words each
     QuantTab qt;                       // final coefficients are written as quantisation indices
 };
-bool launch_dwt(const DwtLaunch &p, hipStream_t st);
+// false: a launch failed, or (*why set) one was refused before it was made
+bool launch_dwt(const DwtLaunch &p, hipStream_t st, const char **why = nullptr);
 
 void launch_t1_cm(const T1CmArgs &a, hipStream_t st);
 void launch_t1_items(const T1ItemArgs &a, hipStream_t st);

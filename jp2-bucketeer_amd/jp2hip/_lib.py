@@ -267,6 +267,10 @@ def tiff_pixels(path) -> int:
 
 
 def recipe(conversion: int, **overrides) -> Recipe:
+    """The default recipe of `conversion` with `overrides` applied field by
+    field (jp2hip.h, jp2hip_recipe).  ``tile_w=0, tile_h=0`` is the untiled
+    recipe: one tile for the whole image, sized by the encode to the smallest
+    multiples of 2^levels not below the image's width and height."""
     r = Recipe()
     lib().jp2hip_recipe_init(byref(r), conversion)
     for k, v in overrides.items():
