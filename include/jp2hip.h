@@ -198,8 +198,21 @@ typedef struct jp2hip_stats {
     int64_t stream_pool_bytes; /* tier-1 decision-stream pool held by the context */
     int64_t stream_need_bytes; /* ... of which this encode's coded planes took    */
     int32_t pool_grows;   /* encodes repeated because the pool was short (0..2) */
-    int32_t reserved;
+    int32_t reused;       /* what this encode found in place on its context     */
+                          /* (JP2HIP_REUSED_*); it records the branches taken   */
+                          /* and steers nothing                                  */
 } jp2hip_stats;
+
+/* jp2hip_stats.reused, a bit set */
+#define JP2HIP_REUSED_PLAN 1         /* the plan came from the context's cache          */
+#define JP2HIP_REUSED_FRONT_TABLES 2 /* the plan's tables were resident (block table,   */
+                                     /* weights, tile-component sizes, group table)     */
+#define JP2HIP_REUSED_T2_TABLES 4    /* the tier-2 tables were resident                 */
+#define JP2HIP_REUSED_STRIPS 8       /* the strip offsets were not uploaded again       */
+#define JP2HIP_AFTER_TRIM 16         /* the previous encode on this context ended by    */
+                                     /* releasing its device buffers                    */
+#define JP2HIP_AFTER_FAILURE 32      /* the previous call on this context failed after  */
+                                     /* its encode had begun                            */
 
 const char *jp2hip_version(void);
 

@@ -44,6 +44,10 @@ struct jp2hip_ctx {
     size_t dev_total = 0;  // the device's memory (hipMemGetInfo at create)
     std::vector<size_t> needs;  // what the last encodes asked for (the context's usual image)
     int64_t reclaimed = 0;      // times another context took this one's idle buffers
+    // jp2hip_stats.reused: how the last call that began an encode ended
+    // (JP2HIP_AFTER_TRIM, JP2HIP_AFTER_FAILURE; set by EncodeEnd), and the
+    // current encode's bits (begin takes `ended` over; the plan cache adds its own)
+    int ended = 0, reused = 0;
     ~jp2hip_ctx() {
         for (jp2hip_ctx *p : peers) jp2hip_destroy(p);
     }
@@ -75,11 +79,12 @@ struct EncodeEnd {
     ~EncodeEnd() {
         if (!ctx) return;
         if (!ok) ctx->gpu.quiesce();
+        ctx->ended = ok ? 0 : JP2HIP_AFTER_FAILURE;
         if (ok) jp2hip::record_need(ctx->needs, ctx->gpu.need_bytes());
         const size_t limit = jp2hip::keep_limit(ctx->needs, ctx->mem_soft);  // (mem_policy.h)
         if (ctx->gpu.device_bytes() > limit) {
             ctx->gpu.quiesce();
-            ctx->gpu.trim(limit);
+            if (ctx->gpu.trim(limit)) ctx->ended |= JP2HIP_AFTER_TRIM;
         }
     }
 };

@@ -92,6 +92,8 @@ int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conv
     meta = source_meta(*lay);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
     ctx->gpu.take_waits();     // count this encode's host waits (stats)
     ctx->gpu.begin_encode();
+    ctx->reused = ctx->ended;  // (stats: how the call before this one ended)
+    ctx->ended = 0;
     end.ctx = ctx;
     return 0;
 }
@@ -169,6 +171,7 @@ int finish_part(jp2hip_ctx *ctx, const FilePart &fp, const SourceMeta &meta, std
     stats->stream_need_bytes = sum.stream_need;
     stats->stream_pool_bytes = (int64_t)ctx->gpu.stream_pool_bytes();
     stats->pool_grows = ctx->gpu.take_pool_grows();
+    stats->reused = ctx->reused | ctx->gpu.reuse_bits();
     return 0;
 }
 
@@ -203,6 +206,8 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         pc.rc = rc;
         pc.w = lay->width; pc.h = lay->height; pc.nc = lay->components; pc.bits = lay->bits;
         pc.valid = true;
+    } else {
+        ctx->reused |= JP2HIP_REUSED_PLAN;
     }
     const Plan &plan = pc.plan;
     const bool prof = ctx->cfg.profile != 0;

@@ -538,6 +538,8 @@ bool GpuEncoder::front_upload(const FrontJob &j, std::string &err) {
         if (!h2d(strips.ptr, lay.strip_offsets, sizeof(uint64_t) * lay.nstrips, err)) return false;
         strips_host.assign(lay.strip_offsets, lay.strip_offsets + lay.nstrips);
         strips_dev = strips.ptr;
+    } else if (!reuse_front_noted) {
+        reuse |= JP2HIP_REUSED_STRIPS;
     }
     // the plan's tables stay resident while the context encodes the same
     // geometry (plan.gen; buffers only grow, so they are still in place)
@@ -562,7 +564,10 @@ bool GpuEncoder::front_upload(const FrontJob &j, std::string &err) {
         if (!ensure<int32_t>(grptab, gtab.size(), err) || !h2d(grptab.ptr, gtab.data(), sizeof(int32_t) * gtab.size(), err))
             return false;
         front_gen = plan.gen;
+    } else if (!reuse_front_noted) {
+        reuse |= JP2HIP_REUSED_FRONT_TABLES;
     }
+    reuse_front_noted = true;
     // (the error word is zeroed by k_quant, which every encode with blocks runs)
     if (!nb) {
         HIPCHECK(hipMemsetAsync(this->err.ptr, 0, sizeof(int), stream));

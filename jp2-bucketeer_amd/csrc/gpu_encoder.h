@@ -82,7 +82,13 @@ class GpuEncoder {
     void begin_encode() {
         for (DevBuf *b : bufs()) b->want = 0;
         expand_timed = false;
+        reuse = 0;
+        reuse_front_noted = false;
     }
+    // what this encode found resident (jp2hip_stats.reused: the
+    // JP2HIP_REUSED_* bits of the front's tables, the tier-2 tables and the
+    // strip offsets); a record of the branches taken, read by nothing else
+    int reuse_bits() const { return reuse; }
     size_t need_bytes() {
         size_t n = 0;
         for (DevBuf *b : bufs()) n += b->want;
@@ -261,6 +267,8 @@ class GpuEncoder {
     bool t2_wave = true;  // precincts of <= 64 blocks: k_t2_wave (layer assignment fused in)
     bool t2_seq = false;  // a progression order other than RPCL: t2seq holds its forward map
     uint64_t front_gen = 0, t2_gen = 0;  // plan generation whose tables are resident
+    int reuse = 0;                   // reuse_bits() of the current encode
+    bool reuse_front_noted = false;  // (its first run_front is the one noted: a repeat finds its own uploads)
     T2Summary *h_sum = nullptr;
     int64_t *h_tot = nullptr;  // pinned [8]: t1 total, -, k_t1_mq span[2], unpack error, segment tail[2]
     bool profiled = false;

@@ -1311,7 +1311,10 @@ bool GpuEncoder::t2_load(const Plan &plan, const T2Tables &T, std::string &err) 
         if (!ensure<uint32_t>(t2ticket, 1, err)) return false;
         HIPCHECK(hipMemsetAsync(t2ticket.ptr, 0, sizeof(uint32_t), stream));
     }
-    if (plan.gen && plan.gen == t2_gen) return true;  // resident (same plan, same tables)
+    if (plan.gen && plan.gen == t2_gen) {  // resident (same plan, same tables)
+        reuse |= JP2HIP_REUSED_T2_TABLES;
+        return true;
+    }
     t2_gen = 0;
     if (!h2d(t2prec.ptr, T.prec.data(), sizeof(PrecDesc) * T.prec.size(), err) ||
         !h2d(t2tp.ptr, T.tp.data(), sizeof(TpDesc) * T.tp.size(), err) ||

@@ -21,6 +21,8 @@ FORMAT_J2K, FORMAT_JP2, FORMAT_JPX = 0, 1, 2
 PHOTO_DEFAULT, PHOTO_WHITE_IS_ZERO, PHOTO_PALETTE = 0, 1, 2
 # Recipe.progression (JP2HIP_ORDER_*: COD's progression order)
 ORDER_LRCP, ORDER_RLCP, ORDER_RPCL, ORDER_PCRL, ORDER_CPRL = 0, 1, 2, 3, 4
+# Stats.reused (JP2HIP_REUSED_*, JP2HIP_AFTER_*): what an encode found in place
+REUSED_PLAN, REUSED_FRONT_TABLES, REUSED_T2_TABLES, REUSED_STRIPS, AFTER_TRIM, AFTER_FAILURE = 1, 2, 4, 8, 16, 32
 
 
 class Jp2hipError(OSError):
@@ -111,7 +113,7 @@ class Stats(Structure):
                 ("out_bytes", c_int64), ("rate_iterations", c_int32), ("host_waits", c_int32),
                 ("t1_cm_ms", c_double), ("t1_mq_ms", c_double), ("mq_decisions", c_int64),
                 ("stream_pool_bytes", c_int64), ("stream_need_bytes", c_int64), ("pool_grows", c_int32),
-                ("reserved", c_int32)]
+                ("reused", c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
