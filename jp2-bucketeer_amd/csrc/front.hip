@@ -135,8 +135,233 @@ struct QuantArgs {
 };
 
 constexpr int kQuantWaves = 2;  // code-blocks (waves) per workgroup
-// The coefficient plane holds the quantisation indices the DWT wrote
-// (sign-magnitude, 16-bit words when Q16: QuantTab::q16)
+
+// The bit-plane masks of a column whose magnitudes fit BITS (8 or 16) bits,
+// by a bit-matrix transpose in registers; its cost does not depend on the
+// number of planes.  Word i of W packs rows i, i + NW, ... (32 / BITS fields
+// of BITS bits, NW = ROWS * BITS / 32 words).  log2(BITS) rounds of masked
+// swaps between words i and i + s exchange bit s of the word index with bit s
+// of the bit position; then word b (and, with 64 rows, word BITS + b) holds
+// plane b: field k, bit i of word b + BITS * j = row i + BITS * j + NW * k.
+// Two v_perm_b32 order the fields by row.
+template <int ROWS, int BITS>
+__device__ __forceinline__ void quant_transpose(uint32_t (&W)[ROWS * BITS / 32], int P, uint64_t valid, uint64_t *planes,
+                                                uint64_t *BT, int lane) {
+    constexpr int NW = ROWS * BITS / 32;
+    static_assert((BITS == 8 || BITS == 16) && (ROWS == 32 || ROWS == 64) && NW >= BITS, "quant_transpose");
+#pragma unroll
+    for (int s = 1; s < BITS; s <<= 1) {
+        const uint32_t m = s == 1 ? 0x55555555u : s == 2 ? 0x33333333u : s == 4 ? 0x0F0F0F0Fu : 0x00FF00FFu;
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            if (i & s) continue;
+            const uint32_t x = W[i], y = W[i + s];
+            W[i] = (x & m) | ((y << s) & ~m);
+            W[i + s] = ((x >> s) & m) | (y & ~m);
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < BITS; b++) {
+        if (b >= P) break;
+        uint32_t lo = W[b], hi = 0;
+        if constexpr (ROWS == 64) {
+            // fields of word b: rows 0.., 2 BITS..; of word BITS + b: rows BITS.., 3 BITS..
+            constexpr uint32_t sel_lo = BITS == 8 ? 0x05010400u : 0x05040100u;
+            constexpr uint32_t sel_hi = BITS == 8 ? 0x07030602u : 0x07060302u;
+            lo = __builtin_amdgcn_perm(W[BITS + b], W[b], sel_lo);
+            hi = __builtin_amdgcn_perm(W[BITS + b], W[b], sel_hi);
+        }
+        const uint64_t m = (((uint64_t)hi << 32) | lo) & valid;
+        planes[b * 64 + lane] = m;
+        BT[(size_t)b * 64 + lane] = m;
+    }
+}
+
+// What the two front halves below share once the column's magnitudes are
+// OR-ed into vor and its signs are in sgcol: the block's number of magnitude
+// bits (uniform: P and the plane loop stay scalar) and the sign column.
+// Column masks (lane c, bit y = row y): BT[p][c] = bit p of the column, then
+// the sign column SGT[c] -- the layout the tier-1 context modelling reads
+// (t1.hip k_t1_cm3)
+__device__ __forceinline__ int quant_planes_and_signs(const QuantArgs &a, const BlockDesc &d, int b, int lane, uint32_t vor,
+                                                      uint64_t sgcol, uint64_t *BT) {
+    vor = wave_or_u32(vor);  // a DPP reduction
+    const int P = __builtin_amdgcn_readfirstlane(vor ? 32 - __clz(vor) : 0);
+    if (lane == 0) a.P[b] = (uint8_t)P;
+    uint64_t *SGT = BT + (size_t)d.Mb * 64;
+    SGT[lane] = sgcol;
+    return P;
+}
+
+// The front half of k_quant for a block of at most ROWS rows (64 or 32): the
+// column load, the sign / magnitude split, the bit-plane masks (to LDS, for
+// the distortion sums, and to HBM) and the sign column.  Returns the block's
+// number of magnitude bits.  The coefficient plane holds the quantisation
+// indices the DWT wrote, sign-magnitude.
+//
+// The lane's column stays in registers for the bit-plane passes: the indices
+// are read from HBM once, all ROWS row loads in flight at once; rows past
+// the block end re-read its last row and lanes past its width read column 0
+// -- values of the block, so its magnitude bits are unchanged -- and are
+// cleared from the masks (`valid`), not row by row.  The sign bit is taken as
+// stored: a -0.0 quantises to 0, and a zero's sign is never coded.
+//
+// 16-bit index plane (QuantTab::q16): rows i and i + ROWS / 2 share a word from
+// the start, which is the packing of the 16-bit transpose and one v_perm_b32
+// away from that of the 8-bit one.
+template <int ROWS>
+__device__ __forceinline__ int quant_columns16(const QuantArgs &a, const BlockDesc &d, int b, int lane, bool act, bool keep_sm,
+                                               uint64_t valid, int32_t *sm, uint64_t *planes) {
+    static_assert(ROWS == 64 || ROWS == 32, "quant_columns16: 64 or 32 rows");
+    constexpr int H = ROWS / 2;
+    const size_t e0 = (size_t)d.tc * a.plane_w * a.plane_h + (size_t)d.y0 * a.plane_w + d.x0;
+    const uint16_t *src = (const uint16_t *)a.coef + e0;
+    const int cl = act ? lane : 0;
+    const int hm1 = d.h - 1;
+    uint32_t W[H];
+#pragma unroll
+    for (int i = 0; i < H; i++) {
+        // the two rows as the elements of a 2 x 16-bit vector: packed as they
+        // arrive, so the column never takes a register per row
+        typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+        u16x2 w;
+        w.x = src[(size_t)min(i, hm1) * a.plane_w + cl];
+        w.y = src[(size_t)min(i + H, hm1) * a.plane_w + cl];
+        W[i] = __builtin_bit_cast(uint32_t, w);
+    }
+    // The sign bits, 15 and 31 of every word, two ops a word: word i < 16
+    // shifted right by 15 - i drops them at bits i and 16 + i of s0; word i
+    // >= 16 shifted by 31 - i at bits i - 16 and i of s1.  So the low halves
+    // of (s0, s1) are the signs of rows 0..31 and the high halves those of
+    // rows H.. .  The magnitudes keep their sign bits for now.
+    uint32_t s0 = 0, s1 = 0, vor = 0;
+#pragma unroll
+    for (int i = 0; i < H; i++) {
+        if (i < 16) s0 |= (W[i] >> (15 - i)) & (0x00010001u << i);
+        else s1 |= (W[i] >> (31 - i)) & (0x00010001u << (i - 16));
+        vor |= W[i];
+    }
+    uint64_t sgcol = s0;  // 32 rows: bits i and 16 + i are rows i and H + i
+    if constexpr (ROWS == 64)
+        sgcol = ((uint64_t)__builtin_amdgcn_perm(s1, s0, 0x07060302u) << 32) | __builtin_amdgcn_perm(s1, s0, 0x05040100u);
+    sgcol &= valid;
+    uint64_t *BT = a.bp + d.bp_off;
+    const int P = quant_planes_and_signs(a, d, b, lane, (vor | (vor >> 16)) & 0x7FFFu, sgcol, BT);
+    if (keep_sm) {  // debug dumps only (Mb <= 15 here): the rows read again, not held in registers for this
+        for (int y = 0; y < d.h; y++) {
+            const uint32_t raw = src[(size_t)y * a.plane_w + cl];
+            sm[y * 64] = act ? (int32_t)((raw & 0x7FFFu) | (raw >> 15) << 31) : 0;
+        }
+    }
+    if (P > 8) {
+#pragma unroll
+        for (int i = 0; i < H; i++) W[i] &= 0x7FFF7FFFu;
+        quant_transpose<ROWS, 16>(W, P, valid, planes, BT, lane);
+    } else if (P > 0) {
+        // bytes of rows i, i + Q, i + 2Q, i + 3Q (Q = ROWS / 4) from the words
+        // of rows (i, i + 2Q) and (i + Q, i + 3Q): the low bytes of their
+        // halves, which leaves the sign bits behind
+        constexpr int Q = ROWS / 4;
+        uint32_t B[Q];
+#pragma unroll
+        for (int i = 0; i < Q; i++) B[i] = __builtin_amdgcn_perm(W[i + Q], W[i], 0x06020400u);
+        quant_transpose<ROWS, 8>(B, P, valid, planes, BT, lane);
+    }
+    return P;
+}
+
+// 32-bit index plane (sources deeper than 8 bits, small quantiser steps): up
+// to 31 planes, by the nibble spread.
+template <int ROWS>
+__device__ __forceinline__ int quant_columns32(const QuantArgs &a, const BlockDesc &d, int b, int lane, bool act, bool keep_sm,
+                                               uint64_t valid, int32_t *sm, uint64_t *planes) {
+    static_assert(ROWS == 64 || ROWS == 32, "quant_columns32: 64 or 32 rows");
+    const size_t e0 = (size_t)d.tc * a.plane_w * a.plane_h + (size_t)d.y0 * a.plane_w + d.x0;
+    const uint32_t *src = (const uint32_t *)a.coef + e0;
+    const int cl = act ? lane : 0;
+    const int hm1 = d.h - 1;
+    uint32_t col[ROWS];
+#pragma unroll
+    for (int y = 0; y < ROWS; y++) col[y] = src[(size_t)min(y, hm1) * a.plane_w + cl];
+    // magnitudes in col[], the signs straight into the sign column
+    uint32_t sg_lo = 0, sg_hi = 0, vor = 0;
+#pragma unroll
+    for (int y = 0; y < ROWS; y++) {
+        const uint32_t raw = col[y];
+        if (y < 32) sg_lo |= (raw >> 31) << y;
+        else sg_hi |= (raw >> 31) << (y - 32);
+        col[y] = raw & 0x7FFFFFFFu;
+        vor |= col[y];
+    }
+    const uint64_t sgcol = (((uint64_t)sg_hi << 32) | sg_lo) & valid;
+    if (keep_sm) {
+#pragma unroll
+        for (int y = 0; y < ROWS; y++)
+            if (y < d.h) sm[y * 64] = act ? (int32_t)(col[y] | (uint32_t)((sgcol >> y) & 1u) << 31) : 0;
+    }
+    uint64_t *BT = a.bp + d.bp_off;
+    const int P = quant_planes_and_signs(a, d, b, lane, vor, sgcol, BT);
+    // Four planes at a time: a row's 4 bits are spread to the 4 bytes of a
+    // word by one multiply (nib * 0x204081 & 0x01010101), so G[g] collects
+    // rows 8g..8g+7 with plane p0+k in byte k; each plane's 64-bit mask is
+    // then byte k of G[0..7], gathered by v_perm_b32 (4 ops per row group of
+    // 4 planes instead of 2 per row and plane)
+    for (int p0 = 0; p0 < P; p0 += 4) {
+        uint32_t G[ROWS / 8];
+#pragma unroll
+        for (int g = 0; g < ROWS / 8; g++) {
+            uint32_t acc = 0;
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                acc |= (__umul24(__builtin_amdgcn_ubfe(col[8 * g + i], (uint32_t)p0, 4u), 0x00204081u) & 0x01010101u) << i;
+            G[g] = acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int p = p0 + k;
+            if (p >= P) break;
+            // bytes k of (G0, G1) and (G2, G3) -> low halves; the pair merged
+            const uint32_t sel = (uint32_t)k | ((uint32_t)(k + 4) << 8) | 0x0C0C0000u;
+            const uint32_t lo = __builtin_amdgcn_perm(G[1], G[0], sel) | (__builtin_amdgcn_perm(G[3], G[2], sel) << 16);
+            uint32_t hi = 0;
+            if constexpr (ROWS == 64)
+                hi = __builtin_amdgcn_perm(G[5], G[4], sel) | (__builtin_amdgcn_perm(G[7], G[6], sel) << 16);
+            const uint64_t m = (((uint64_t)hi << 32) | lo) & valid;
+            planes[p * 64 + lane] = m;
+            BT[(size_t)p * 64 + lane] = m;
+        }
+    }
+    return P;
+}
+
+// The sum over the wave of one row of the plane loop's per-lane partials: row
+// rho = 2 * plane + k (k = 0: sv, 1: sl), the 64 dwords w32[128 plane + 2 j +
+// k], int32 each, added up in 64 bits.  R = 2^lgR >= the number of rows (4..64)
+// lanes take a row each, 64 / R lanes per row; a lane walks R entries of its
+// row, starting R entries apart from the row's other lanes and one entry
+// further for every lane, so that the reads of a step spread over the banks;
+// the row's lanes then add their parts (every lane of a row returns the row's
+// total).  Rows past `rows` read row 0 and return nothing of use.
+__device__ __forceinline__ int64_t quant_row_sum(const int32_t *w32, int rows, int lgR, int lane) {
+    const int R = 1 << lgR;
+    const int rho = lane & (R - 1);
+    const int r = rho < rows ? rho : 0;
+    const int base = (r >> 1) * 128 + (r & 1);
+    const int j0 = (lane >> lgR) << lgR;
+    int64_t acc = 0;
+#pragma unroll 4
+    for (int t = 0; t < R; t++) {
+        const int j = j0 + ((t + lane) & (R - 1));
+        acc += w32[base + 2 * j];
+    }
+    for (int o = R; o < 64; o <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)acc, o, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)((uint64_t)acc >> 32), o, 64);
+        acc += (int64_t)(((uint64_t)hi << 32) | lo);
+    }
+    return acc;
+}
+
 template <bool REV, bool Q16>
 __global__ void __launch_bounds__(64 * kQuantWaves) k_quant(QuantArgs a) {
     extern __shared__ uint64_t lds_planes[];  // [wave][plane][lane], a.max_mb planes per wave
@@ -151,93 +376,20 @@ __global__ void __launch_bounds__(64 * kQuantWaves) k_quant(QuantArgs a) {
     BlockDesc d = a.blocks[b];
     int lane = threadIdx.x & 63;
     bool act = lane < d.w;
-    // the block's first row (wave-uniform: each row load is a scalar base +
-    // the lane's column offset, no per-row address registers)
-    const size_t e0 = (size_t)d.tc * a.plane_w * a.plane_h + (size_t)d.y0 * a.plane_w + d.x0;
-    const int cl = act ? lane : 0;
     int32_t *sm = a.sm + d.sm_off + lane;
     // the sign-magnitude copy is read only by the 64-bit distortion path of
     // planes above 23 (below) and by the debug dumps
     const bool keep_sm = a.keep_sm || d.Mb > 24;
-    uint32_t vmax = 0;
-    // the lane's column stays in registers (sign | magnitude) for the
-    // bit-plane and distortion passes: the indices are read from HBM once.
-    // All 64 row loads are in flight at once; rows past the block end
-    // re-read its last row and lanes past its width read column 0 -- values
-    // of the block, so its maximum is unchanged -- and are cleared from the
-    // bit-plane masks (`valid`), not row by row.
-    uint32_t col[64];
-    const int hm1 = d.h - 1;
-    if constexpr (Q16) {
-        const uint16_t *src = (const uint16_t *)a.coef + e0;
-#pragma unroll
-        for (int y = 0; y < 64; y++) col[y] = src[(size_t)min(y, hm1) * a.plane_w + cl];
-    } else {
-        const uint32_t *src = (const uint32_t *)a.coef + e0;
-#pragma unroll
-        for (int y = 0; y < 64; y++) col[y] = src[(size_t)min(y, hm1) * a.plane_w + cl];
-    }
-    // magnitudes in col[], the signs straight into the sign column (the sign
-    // bit as stored: a -0.0 quantises to 0, and a zero's sign is never coded)
-    constexpr int kSb = Q16 ? 15 : 31;
-    uint32_t sg_lo = 0, sg_hi = 0;
-#pragma unroll
-    for (int y = 0; y < 64; y++) {
-        const uint32_t raw = col[y];
-        const uint32_t v = raw & ((1u << kSb) - 1u);
-        if (y < 32) sg_lo |= (raw >> kSb) << y;
-        else sg_hi |= (raw >> kSb) << (y - 32);
-        col[y] = v;
-        vmax = max(vmax, v);
-    }
     const uint64_t hmask = d.h >= 64 ? ~0ull : ((1ull << d.h) - 1ull);
     const uint64_t valid = act ? hmask : 0ull;  // rows < h of columns < w
-    const uint64_t sgcol = (((uint64_t)sg_hi << 32) | sg_lo) & valid;
-    if (keep_sm) {
-#pragma unroll
-        for (int y = 0; y < 64; y++)
-            if (y < d.h) sm[y * 64] = act ? (int32_t)(col[y] | (uint32_t)((sgcol >> y) & 1u) << 31) : 0;
-    }
-    // the magnitude bits of the block = those of the OR of its magnitudes
-    // (a DPP reduction; uniform: P and the plane loop stay scalar)
-    vmax = wave_or_u32(vmax);
-    const int P = __builtin_amdgcn_readfirstlane(vmax ? 32 - __clz(vmax) : 0);
-    if (lane == 0) a.P[b] = (uint8_t)P;
-    // column masks (lane c, bit y = row y): BT[p][c] = bit p of the
-    // column, then the sign column SGT[c] -- the layout the tier-1 context
-    // modelling reads (t1.hip k_t1_cm3)
-    uint64_t *BT = a.bp + d.bp_off;
-    uint64_t *SGT = BT + (size_t)d.Mb * 64;
-    SGT[lane] = sgcol;
-    // every plane's column mask, kept in LDS for the distortion sums below.
-    // Four planes at a time: a row's 4 bits are spread to the 4 bytes of a
-    // word by one multiply (nib * 0x204081 & 0x01010101), so G[g] collects
-    // rows 8g..8g+7 with plane p0+k in byte k; each plane's 64-bit mask is
-    // then byte k of G[0..7], gathered by v_perm_b32 (4 ops per row group of
-    // 4 planes instead of 2 per row and plane)
-    for (int p0 = 0; p0 < P; p0 += 4) {
-        uint32_t G[8];
-#pragma unroll
-        for (int g = 0; g < 8; g++) {
-            uint32_t acc = 0;
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-                acc |= (__umul24(__builtin_amdgcn_ubfe(col[8 * g + i], (uint32_t)p0, 4u), 0x00204081u) & 0x01010101u) << i;
-            G[g] = acc;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int p = p0 + k;
-            if (p >= P) break;
-            // bytes k of (G0, G1) and (G2, G3) -> low halves; the pair merged
-            const uint32_t sel = (uint32_t)k | ((uint32_t)(k + 4) << 8) | 0x0C0C0000u;
-            const uint32_t lo = __builtin_amdgcn_perm(G[1], G[0], sel) | (__builtin_amdgcn_perm(G[3], G[2], sel) << 16);
-            const uint32_t hi = __builtin_amdgcn_perm(G[5], G[4], sel) | (__builtin_amdgcn_perm(G[7], G[6], sel) << 16);
-            const uint64_t m = (((uint64_t)hi << 32) | lo) & valid;
-            planes[p * 64 + lane] = m;
-            BT[(size_t)p * 64 + lane] = m;
-        }
-    }
+    // short blocks (the deep levels' bands) load and transpose only 32 rows
+    int P;
+    if constexpr (Q16)
+        P = d.h > 32 ? quant_columns16<64>(a, d, b, lane, act, keep_sm, valid, sm, planes)
+                     : quant_columns16<32>(a, d, b, lane, act, keep_sm, valid, sm, planes);
+    else
+        P = d.h > 32 ? quant_columns32<64>(a, d, b, lane, act, keep_sm, valid, sm, planes)
+                     : quant_columns32<32>(a, d, b, lane, act, keep_sm, valid, sm, planes);
     constexpr bool lossless = REV;
     constexpr int dd = lossless ? 0 : 1;  // reconstruction offset, half-units
     const bool wcol = lane < d.w;
@@ -253,67 +405,103 @@ __global__ void __launch_bounds__(64 * kQuantWaves) k_quant(QuantArgs a) {
     // sum_N v = sum_{q<=p} 2^q |N & B[q]|, sum_R +-l = sum_{q<p} 2^q (|R1 &
     // B[q]| - |R0 & B[q]|), int32 per lane up to p = 23.  The slope-prediction
     // counts (oracle plane_stats): significant samples, and insignificant
-    // samples with a significant 8-neighbour.
-    for (int p = P - 1; p >= 0; p--) {
-        const uint64_t Bp = planes[p * 64 + lane];
-        const uint64_t N = Bp & ~colS, R1 = colS & Bp;
-        uint32_t nb1 = (uint32_t)__popcll(R1);  // refined samples with bit p set
-        int64_t ref = 0, sig = 0;
-        int32_t sv = 0, sl = 0;
-        if (p <= 23) {
-            sv = __popcll(N) << p;
-            for (int q = 0; q < p; q++) {
-                const uint64_t Bq = planes[q * 64 + lane];
-                sv += __popcll(N & Bq) << q;
-                sl += (2 * __popcll(R1 & Bq) - __popcll(colS & Bq)) * (1 << q);
-            }
-        } else {
-            // 64-bit gains per row, the column re-read from the sign-magnitude
-            // copy (never for <= 16-bit sources)
-            for (int y = 0; y < d.h; y++) {
-                const uint32_t v = (uint32_t)sm[y * 64] & 0x7FFFFFFFu;
-                const uint32_t hi = v >> p;
-                if (hi == 0) continue;
-                const int64_t g = dist_gain(v, p, lossless);
-                if (hi == 1) sig += g;
-                else ref += g;
-            }
-        }
-        colS |= Bp;
+    // samples with a significant 8-neighbour; their wave totals by DPP scans,
+    // cS and cN (<= 4096 each) sharing one scan.
+    uint32_t cS, cN, nb1;
+    auto plane_counts = [&]() {
         // insignificant samples with a significant 8-neighbour (rows < h,
         // columns < w)
         // (DPP whole-wave shifts on every lane: lanes 0 / 63 receive 0)
         const uint64_t Lc = wave_shr1(colS), Rc = wave_shl1(colS);
         const uint64_t H = colS | Lc | Rc;
-        uint32_t cN = wcol ? (uint32_t)__popcll((H | (H << 1) | (H >> 1)) & ~colS & hmask) : 0u;
-        uint32_t cS = (uint32_t)__popcll(colS);
-        // wave totals by DPP scans; cS and cN (<= 4096 each) share one scan
-        {
-            const uint32_t both = wave_sum_u32(cS | (cN << 16));
-            cS = both & 0xFFFFu;
-            cN = both >> 16;
-            nb1 = wave_sum_u32(nb1);
+        const uint32_t n = wcol ? (uint32_t)__popcll((H | (H << 1) | (H >> 1)) & ~colS & hmask) : 0u;
+        const uint32_t both = wave_sum_u32((uint32_t)__popcll(colS) | (n << 16));
+        cS = both & 0xFFFFu;
+        cN = both >> 16;
+        nb1 = wave_sum_u32(nb1);
+    };
+    int p = P - 1;
+    // Planes above 23 (never for <= 16-bit sources): 64-bit gains per row,
+    // the column re-read from the sign-magnitude copy, summed over the wave
+    // plane by plane.
+    for (; p > 23; p--) {
+        const uint64_t Bp = planes[p * 64 + lane];
+        nb1 = (uint32_t)__popcll(colS & Bp);
+        int64_t ref = 0, sig = 0;
+        for (int y = 0; y < d.h; y++) {
+            const uint32_t v = (uint32_t)sm[y * 64] & 0x7FFFFFFFu;
+            const uint32_t hi = v >> p;
+            if (hi == 0) continue;
+            const int64_t g = dist_gain(v, p, lossless);
+            if (hi == 1) sig += g;
+            else ref += g;
         }
-        if (p <= 23) {
-            const int64_t SV = wave_sum64(sv), SL = wave_sum64(sl);
-            const int64_t n1 = cS - cnt_above, nr1 = nb1, nr0 = cnt_above - nb1, q = (int64_t)1 << p;
-            if (lossless && p == 0) {
-                sig = 4 * n1;
-                ref = 4 * nr0;
-            } else {
-                sig = q * (12 * SV + (6 * dd - 9 * q) * n1);
-                ref = q * (4 * SL + nr1 * (2 * dd - q) + nr0 * (3 * q - 2 * dd));
-            }
-        } else {
-            ref = wave_sum64(ref);
-            sig = wave_sum64(sig);
-        }
+        colS |= Bp;
+        plane_counts();
+        ref = wave_sum64(ref);
+        sig = wave_sum64(sig);
         if (lane == 0) {
             a.est[(size_t)b * 32 + p] = 16u * cnt_above + 56u * (cS - cnt_above) + 5u * cN;
             a.dref[(size_t)b * 32 + p] = ref;
             a.dsig[(size_t)b * 32 + p] = sig;
         }
         cnt_above = cS;
+    }
+    // Planes 23 and below.  The lane's sv and sl are not summed over the wave
+    // here: they go to planes[p][lane], which is dead once plane p is done
+    // (lower planes read only planes[q], q < p), and one reduction per block
+    // follows the loop.  Lane p keeps plane p's three counts for it.
+    const int Pn = p + 1;  // min(P, 24)
+    uint32_t my_cS = 0, my_nb1 = 0, my_above = 0;
+    for (; p >= 0; p--) {
+        const uint64_t Bp = planes[p * 64 + lane];
+        const uint64_t N = Bp & ~colS, R1 = colS & Bp;
+        nb1 = (uint32_t)__popcll(R1);  // refined samples with bit p set
+        int32_t sv = __popcll(N) << p, sl = 0;
+        for (int q = 0; q < p; q++) {
+            const uint64_t Bq = planes[q * 64 + lane];
+            sv += __popcll(N & Bq) << q;
+            sl += (2 * __popcll(R1 & Bq) - __popcll(colS & Bq)) * (1 << q);
+        }
+        colS |= Bp;
+        planes[p * 64 + lane] = (uint64_t)(uint32_t)sv | ((uint64_t)(uint32_t)sl << 32);
+        plane_counts();
+        if (lane == 0) a.est[(size_t)b * 32 + p] = 16u * cnt_above + 56u * (cS - cnt_above) + 5u * cN;
+        if (lane == p) {
+            my_cS = cS;
+            my_nb1 = nb1;
+            my_above = cnt_above;
+        }
+        cnt_above = cS;
+    }
+    // The block's sums: rows 2p (sv) and 2p + 1 (sl), a lane or several a row
+    const int rows = 2 * Pn;
+    if (rows == 0) return;
+    int lgR = 2;
+    while ((1 << lgR) < rows) lgR++;  // rows <= 48
+    const int64_t tot = quant_row_sum((const int32_t *)planes, rows, lgR, lane);
+    // the row totals go through LDS to the lane of their plane (every partial
+    // has been read: the wave's LDS operations complete in order)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane < rows) planes[lane] = (uint64_t)tot;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < Pn) {
+        p = lane;
+        const int64_t SV = (int64_t)planes[2 * p], SL = (int64_t)planes[2 * p + 1];
+        const int64_t n1 = my_cS - my_above, nr1 = my_nb1, nr0 = my_above - my_nb1, q = (int64_t)1 << p;
+        int64_t ref, sig;
+        if (lossless && p == 0) {
+            sig = 4 * n1;
+            ref = 4 * nr0;
+        } else {
+            sig = q * (12 * SV + (6 * dd - 9 * q) * n1);
+            ref = q * (4 * SL + nr1 * (2 * dd - q) + nr0 * (3 * q - 2 * dd));
+        }
+        a.dref[(size_t)b * 32 + p] = ref;
+        a.dsig[(size_t)b * 32 + p] = sig;
     }
 }
 
