@@ -3,10 +3,13 @@
 // before it, between this file's shims and main(); the result is compiled
 // with clang++ -fsanitize=address, and run on zlib
 // streams (levels 0/1/6/9 at every byte alignment) and damaged streams.
+// Given a file name, it runs the records of that file instead: the crafted
+// corpus of tests/inflate_cases.py, as tests/test_inflate_host.py dumps it.
 // [[SHIMS]]
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 #include <algorithm>
 #include <zlib.h>
@@ -38,7 +41,9 @@ using namespace jp2hip;
 // hipMalloc memory may hold zeros, a reused one stale links of another image)
 static int run(const std::vector<uint8_t> &z, int off, const std::vector<uint8_t> &raw,
                uint32_t lnk_init = 0xDEADBEEFu) {
-    std::vector<uint8_t> buf(z.size() + 16, 0xA5);
+    // room for any offset 0..15 and for the stream's last word: the ring is loaded in whole words, so up
+    // to 3 bytes after the stream are read (never used: a stream read past its end is corrupt)
+    std::vector<uint8_t> buf(z.size() + 16 + 3, 0xA5);
     std::memcpy(buf.data() + off, z.data(), z.size());
     std::vector<uint8_t> out(raw.size() + 256);
     std::vector<uint32_t> lnk(raw.size() + 256, lnk_init);
@@ -65,7 +70,62 @@ static int run(const std::vector<uint8_t> &z, int off, const std::vector<uint8_t
     return std::memcmp(out.data(), raw.data(), raw.size()) ? 2 : 0;
 }
 
-int main() {
+// The corpus mode.  The file: "INFC", a count, then per record (32-bit
+// little-endian fields) the name's length and the name, the offset residue
+// modulo 16, cap, 1 for a stream that must be refused, the stream's length and
+// the stream, and for a good stream the cap bytes it decodes to.  A refused
+// stream is also run over link buffers preset to 0, 5 and 0x7FFFFFFF.
+static int run_corpus(const char *path) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { printf("cannot open %s\n", path); return 2; }
+    std::vector<uint8_t> all;
+    uint8_t tmp[65536];
+    for (size_t n; (n = fread(tmp, 1, sizeof tmp, f)) > 0;) all.insert(all.end(), tmp, tmp + n);
+    fclose(f);
+    size_t p = 0;
+    bool short_file = false;
+    auto u32 = [&]() -> uint32_t {
+        if (p + 4 > all.size()) { short_file = true; return 0; }
+        uint32_t v;
+        std::memcpy(&v, all.data() + p, 4);
+        p += 4;
+        return v;
+    };
+    auto bytes = [&](size_t n) {
+        std::vector<uint8_t> v;
+        if (p + n > all.size()) { short_file = true; return v; }
+        v.assign(all.begin() + p, all.begin() + p + n);
+        p += n;
+        return v;
+    };
+    if (all.size() < 8 || std::memcmp(all.data(), "INFC", 4)) { printf("not a corpus file\n"); return 2; }
+    p = 4;
+    const uint32_t count = u32();
+    int fails = 0;
+    for (uint32_t i = 0; i < count && !short_file; i++) {
+        const std::vector<uint8_t> nm = bytes(u32());
+        const std::string name(nm.begin(), nm.end());
+        const uint32_t residue = u32(), cap = u32(), corrupt = u32();
+        const std::vector<uint8_t> z = bytes(u32());
+        const std::vector<uint8_t> want = corrupt ? std::vector<uint8_t>(cap, 0) : bytes(cap);
+        if (short_file || residue > 15) break;
+        if (!corrupt) {
+            const int rc = run(z, (int)residue, want);
+            if (rc) { printf("FAILED %s -> %d\n", name.c_str(), rc); fails++; }
+            continue;
+        }
+        for (uint32_t init : {0xDEADBEEFu, 0u, 5u, 0x7FFFFFFFu}) {
+            const int rc = run(z, (int)residue, want, init);
+            if (rc != 1) { printf("FAILED %s, links preset %u -> %d\n", name.c_str(), init, rc); fails++; }
+        }
+    }
+    if (short_file) { printf("the corpus file ends early\n"); return 2; }
+    printf("%u cases\n%s\n", count, fails ? "FAIL" : "OK");
+    return fails ? 1 : 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1) return run_corpus(argv[1]);
     std::vector<uint8_t> raw(300000);
     uint32_t r = 1;
     for (size_t i = 0; i < raw.size(); i++) {
