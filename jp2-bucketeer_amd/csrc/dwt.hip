@@ -34,12 +34,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
 #include "device_common.h"
 #include "dwt_chunk.h"
 #include "dwt_fetch.h"
+#include "dwt_route.h"
 #include "gpu_encoder.h"
 
 namespace jp2hip {
@@ -51,11 +53,9 @@ namespace jp2hip {
 #define K97 (1.230174104914001f)
 #define INVK97 (0.8128930661159609f)
 
-constexpr int kDwtThreads = 256;
-constexpr int kDwtHalo = 4;           // >= lifting steps (9/7: 4, 5/3: 2)
-constexpr int kDwtLdsWords = 16384;   // 64 KiB: band workgroups for rows <= 1024, tail
-constexpr int kDwtLdsWordsWide = 32768;  // 128 KiB: what the wide instances opt in to (level 1's routes compare with it)
-static_assert(kDwtHalo == kDwtChunkHalo, "one halo, rows and columns");
+// (kDwtThreads, kDwtHalo, the LDS row layouts and every size a launch is
+// given: dwt_route.h)
+static_assert(kDwtRouteLevels == kMaxLevels, "a route holds every level of a plan");
 
 // One lifting step over the LDS rows [ya, yb) of a column set (vertical) or
 // over one row (horizontal).  Sample i of parity `par` is updated from
@@ -140,7 +140,7 @@ struct DwtBandArgs {
     int ll_stride;
     size_t ll_tc;
     const int32_t *tc_w, *tc_h;
-    int level, R;
+    int level;
     int ragged;  // some tile width is not a multiple of 16 (k_dwt_l1s second launch)
     int px_fetch;      // k_dwt_l1s: chunky pixels are loaded with one access each (dwt_fetch.h)
     uint64_t src_end;  // ... none of which ends beyond this source offset
@@ -268,20 +268,8 @@ __device__ __forceinline__ void lift_regs_u(int32_t (&v)[NR], int y0, int H) {
 // staged rows (LDS row r at lds + kPadL + r * ld).  rows(r, o) fills row
 // r's outputs (QRow; false: row r was not staged).  A register
 // variant (16-sample segments, 16-byte stores) measured slower: its stores
-// scatter over many lines per wave-instruction.
-constexpr int kPadL = 4;   // LDS words in front of row 0 (the first segment's left halo)
-// LDS row stride for W samples: a multiple of 4 words (16-byte reads), = 4
-// mod 64 so consecutive rows start on different banks
-__host__ __device__ constexpr int lds_row_stride(int W) { return ((W + 63) & ~63) + 4; }
-constexpr int kPadR = 24;  // LDS words after the last row (the last segment's right halo)
-// Skewed staging layout (k_dwt_l1s): 4 words of padding after every 16
-// samples.  hlift_seg's lanes read 16-sample segments, 16 bytes at a time;
-// in the dense layout the 16 lanes of a ds_read_b128 group sit 16 words
-// apart, so only 4 distinct bank windows serve them (4-way conflicts); at 20
-// words apart every lane of the group has its own 4 banks.
-__host__ __device__ constexpr int skew_x(int x) { return x + ((x >> 4) << 2); }
-__host__ __device__ constexpr int lds_row_stride_skew(int W) { return ((W + 15) >> 4) * 20 + 4; }
-constexpr int kPadLs = 8;  // ... words in front of row 0: segment 0 reads 8 words before its samples
+// scatter over many lines per wave-instruction.  (The row layouts -- kPadL,
+// lds_row_stride, kPadR and the skewed one: dwt_route.h.)
 
 // Where one staged row's outputs go: its low half raw to the next level's LL
 // row `ll` (a non-final level's even rows), or -- like its high half --
@@ -766,28 +754,12 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1(DwtBandArgs a) {
 // in the same order as lift_regs / oracle fwd97_1d (bit-exact): an update
 // whose neighbour lies outside the streamed rows is skipped, as lift_regs
 // leaves a window's edge stale, and never reaches a kept row.
-#ifndef JP2HIP_STREAM_BAND
-#define JP2HIP_STREAM_BAND 64
-#endif
-constexpr int kStreamBand = JP2HIP_STREAM_BAND;
-#ifndef JP2HIP_L1S_SKEW
-#define JP2HIP_L1S_SKEW 1  // the skewed staging layout (hlift_seg's reads conflict-free)
-#endif
-constexpr bool kL1sSkew = JP2HIP_L1S_SKEW != 0;
+// (kStreamBand, kL1sSkew, kL1sRows and their switches: dwt_route.h)
 #ifndef JP2HIP_L1S_PF
 #define JP2HIP_L1S_PF 1  // row pairs fetched ahead (1, 2 or 3; 2 and 3 measured slower: profiles/r06/ab_l1s_prefetch.txt)
 #endif
 constexpr int kL1sPf = JP2HIP_L1S_PF;
 static_assert(kL1sPf >= 1 && kL1sPf <= 3, "JP2HIP_L1S_PF: 1..3");
-#ifndef JP2HIP_L1S_INTERIOR
-#define JP2HIP_L1S_INTERIOR 0  // A/B: the select-free interior lifting path
-#endif
-#ifndef JP2HIP_L1S_R
-#define JP2HIP_L1S_R 4  // rows per horizontal batch (4 or 8)
-#endif
-// (99 VGPRs, 4 waves per SIMD for the C2 variant; a budget for 5 --
-// amdgpu_waves_per_eu(5), 5 VGPRs spilled -- measured no faster: 146.7 vs
-// 146.4 us, profiles/r05/ab_select_fold.txt)
 #ifndef JP2HIP_L1S_CENSUS
 #define JP2HIP_L1S_CENSUS 0  // debug builds: shader cycles per phase of the row pipeline (output to stderr)
 #endif
@@ -997,30 +969,7 @@ __global__ void __launch_bounds__(kDwtThreads) k_dwt_l1s(DwtBandArgs a) {
         if (m + 2 * kL1sPf - 1 < e) fetch(SA);
         if (m + 2 * kL1sPf < e) fetch(SB);
         L1S_TICK(1);
-        // interior iterations (every step's rows and neighbours inside the
-        // streamed rows and the signal, none at row 0): fixed neighbour slots,
-        // no per-value selects -- the same expressions in the same order
-        if (JP2HIP_L1S_INTERIOR && H > 1 && m - NS - 1 >= s && m < e) {
-#pragma unroll
-            for (int k = 0; k < NS; k++) {
-                const int ti = NWIN - 2 - k;
-#pragma unroll
-                for (int j = 0; j < CPT; j++)
-#pragma unroll
-                    for (int c = 0; c < NC; c++) {
-                        const int32_t lv = w[j][c][ti - 1], rv = w[j][c][ti + 1];
-                        if (REV) {
-                            if (k == 0) w[j][c][ti] -= (lv + rv) >> 1;
-                            else w[j][c][ti] += (lv + rv + 2) >> 2;
-                        } else {
-                            const float cf = k == 0 ? A97 : (k == 1 ? B97 : (k == 2 ? G97 : D97));
-                            float tt = __int_as_float(lv) + __int_as_float(rv);
-                            tt = cf * tt;
-                            w[j][c][ti] = __float_as_int(__int_as_float(w[j][c][ti]) + tt);
-                        }
-                    }
-            }
-        } else if (H > 1) {
+        if (H > 1) {
 #pragma unroll
             for (int k = 0; k < NS; k++) {
                 const int tr = m - 1 - k, ti = NWIN - 2 - k;  // target row, its window slot
@@ -1136,10 +1085,8 @@ struct DwtTailArgs {
 // threads and 21 KB of LDS.  Sized for 128 x 128 levels it took 1 024
 // threads and 82 KB -- half a CU -- and under the bench's load such a
 // workgroup waited ~1.5 ms for a CU to free that much (C2 bench +7-9 %).
-constexpr int kTailThreads = 256;
 constexpr int kTailRG = 16;                                  // rows per vertical item
-constexpr int kTailWords = 4096 + 64 * 4 + kPadL + kPadR;    // padded rows of a <= 64 x 64 level
-constexpr int kTailLL = 1024;                                // the LL of a <= 64 x 64 level
+// (kTailThreads, kTailWords, kTailLL: dwt_route.h)
 template <bool REV>
 __global__ void __launch_bounds__(kTailThreads) k_dwt_tail(DwtTailArgs a) {
     __shared__ __attribute__((aligned(16))) int32_t rows_[kTailWords];  // vertical output, padded rows
@@ -1217,89 +1164,34 @@ __global__ void __launch_bounds__(kTailThreads) k_dwt_tail(DwtTailArgs a) {
     }
 }
 
-template <bool REV, bool INGEST, int RB, int NT>
-static void launch_band(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    static bool wide = false;  // opt in to > 64 KiB dynamic LDS once per instance
-    if (lds > (size_t)kDwtLdsWords * 4 && !wide) {
-        (void)hipFuncSetAttribute((const void *)k_dwt_band<REV, INGEST, RB, NT>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kDwtLdsWordsWide * 4);
-        wide = true;
+// Launches instance K on the grid, workgroup and dynamic LDS of the route's
+// record.  An instance given more than the default 64 KiB opts in first, once
+// per (instance, device): bit d of `opted` is set after the attribute has been
+// set with device d current, so contexts on several host threads may meet
+// here (at worst two of them both set it), and ordinals from 64 up set it at
+// every launch.  Whether this runtime keeps the attribute per device or per
+// process has not been measured; the mask is right under either reading.
+template <auto K, typename Args>
+static void launch_routed(const DwtLevelRoute &r, hipStream_t st, const Args &a) {
+    if (r.lds > (size_t)kDwtLdsWords * 4) {
+        static std::atomic<uint64_t> opted{0};
+        int dev = -1;
+        (void)hipGetDevice(&dev);
+        const uint64_t bit = dev >= 0 && dev < 64 ? 1ull << dev : 0;
+        if (!(opted.load(std::memory_order_acquire) & bit)) {
+            (void)hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      kDwtLdsWordsWide * 4);
+            opted.fetch_or(bit, std::memory_order_release);
+        }
     }
-    hipLaunchKernelGGL((k_dwt_band<REV, INGEST, RB, NT>), g, dim3(NT), lds, st, a);
-}
-#ifndef JP2HIP_BAND_RB
-#define JP2HIP_BAND_RB 16
-#endif
-#ifndef JP2HIP_BAND_NARROW
-#define JP2HIP_BAND_NARROW 128  // levels at most this wide: workgroups of this many threads
-#endif
-constexpr int kBandRb = JP2HIP_BAND_RB;
-// (a level of <= 128 columns in 128-thread workgroups: with 256 threads half
-// of them had no column)
-template <bool REV, bool INGEST>
-static void launch_band_rb(int maxW, dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    if (!INGEST && JP2HIP_BAND_NARROW < kDwtThreads && maxW <= JP2HIP_BAND_NARROW)
-        launch_band<REV, INGEST, kBandRb, (JP2HIP_BAND_NARROW < kDwtThreads ? JP2HIP_BAND_NARROW : kDwtThreads)>(
-            g, lds, st, a);
-    else
-        launch_band<REV, INGEST, kBandRb, kDwtThreads>(g, lds, st, a);
+    hipLaunchKernelGGL(K, dim3(r.gx, r.gy, r.gz), dim3(r.threads), r.lds, st, a);
 }
 
-// the chunked instances (dwt_chunk.h): the LDS of a chunk's staged rows,
-// whatever the level's width; grid z = chunks of the widest tile-component
-constexpr size_t band_chunk_lds(int rows, int C) {
-    return ((size_t)rows * lds_row_stride(dwt_chunk_staged(C)) + kPadL + kPadR) * 4;
-}
-template <bool REV>
-static void launch_band_chunk(dim3 g, hipStream_t st, const DwtBandArgs &a) {
-    constexpr size_t lds = band_chunk_lds(kBandRb, kBandChunkW);
-    static_assert(lds <= (size_t)kDwtLdsWords * 4, "a chunked band fits the default 64 KiB of dynamic LDS");
-    hipLaunchKernelGGL((k_dwt_band<REV, false, kBandRb, kDwtThreads, true>), g, dim3(kDwtThreads), lds, st, a);
-}
-constexpr int kRb1 = 8;  // k_dwt_l1's kept rows per workgroup
-template <bool REV, int NC>
-static void launch_l1_chunk_nc(dim3 g, hipStream_t st, const DwtBandArgs &a) {
-    constexpr size_t lds = band_chunk_lds(NC * kRb1, kL1ChunkW);
-    static_assert(lds <= (size_t)kDwtLdsWordsWide * 4, "a chunked level 1 fits the 128 KiB the instance opts in to");
-    static bool wide = false;
-    if (lds > (size_t)kDwtLdsWords * 4 && !wide) {
-        (void)hipFuncSetAttribute((const void *)k_dwt_l1<REV, NC, kRb1, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kDwtLdsWordsWide * 4);
-        wide = true;
-    }
-    hipLaunchKernelGGL((k_dwt_l1<REV, NC, kRb1, true>), g, dim3(kDwtThreads), lds, st, a);
-}
-template <bool REV>
-static void launch_l1_chunk(int nc, dim3 g, hipStream_t st, const DwtBandArgs &a) {
-    if (nc == 1) launch_l1_chunk_nc<REV, 1>(g, st, a);
-    else if (nc == 2) launch_l1_chunk_nc<REV, 2>(g, st, a);
-    else if (nc == 3) launch_l1_chunk_nc<REV, 3>(g, st, a);
-    else launch_l1_chunk_nc<REV, 4>(g, st, a);
-}
-
-template <bool REV, int NC>
-static void launch_l1_nc(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    static bool wide = false;
-    if (lds > (size_t)kDwtLdsWords * 4 && !wide) {
-        (void)hipFuncSetAttribute((const void *)k_dwt_l1<REV, NC, 8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kDwtLdsWordsWide * 4);
-        wide = true;
-    }
-    hipLaunchKernelGGL((k_dwt_l1<REV, NC, 8>), g, dim3(kDwtThreads), lds, st, a);
-}
+// two launches cover the tiles: widths that are multiples of 16 and the rest
 template <bool REV, int NC, int CPT, int PX>
-static void launch_l1s_px(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    constexpr int RB = JP2HIP_L1S_R;
-    static bool wide = false;
-    if (lds > (size_t)kDwtLdsWords * 4 && !wide) {
-        (void)hipFuncSetAttribute((const void *)k_dwt_l1s<REV, NC, CPT, RB, true, PX>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kDwtLdsWordsWide * 4);
-        (void)hipFuncSetAttribute((const void *)k_dwt_l1s<REV, NC, CPT, RB, false, PX>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kDwtLdsWordsWide * 4);
-        wide = true;
-    }
-    hipLaunchKernelGGL((k_dwt_l1s<REV, NC, CPT, RB, true, PX>), g, dim3(kDwtThreads), lds, st, a);
-    if (a.ragged) hipLaunchKernelGGL((k_dwt_l1s<REV, NC, CPT, RB, false, PX>), g, dim3(kDwtThreads), lds, st, a);
+static void launch_l1s(const DwtLevelRoute &r, hipStream_t st, const DwtBandArgs &a) {
+    launch_routed<k_dwt_l1s<REV, NC, CPT, kL1sRows, true, PX>>(r, st, a);
+    if (a.ragged) launch_routed<k_dwt_l1s<REV, NC, CPT, kL1sRows, false, PX>>(r, st, a);
 #if JP2HIP_L1S_CENSUS
     unsigned long long h[8];
     if (hipStreamSynchronize(st) == hipSuccess &&
@@ -1313,136 +1205,101 @@ static void launch_l1s_px(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs 
     }
 #endif
 }
-template <bool REV, int NC, int CPT>
-static void launch_l1s_c(dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    // one access per chunky pixel unless the source is planar (or smaller than an access)
-    const int px = (a.planar != 2 && a.px_fetch) ? a.bits >> 3 : 0;
-    if (px == 1) launch_l1s_px<REV, NC, CPT, 1>(g, lds, st, a);
-    else if (px == 2) launch_l1s_px<REV, NC, CPT, 2>(g, lds, st, a);
-    else launch_l1s_px<REV, NC, CPT, 0>(g, lds, st, a);
-}
-template <bool REV, int NC>
-static void launch_l1s_nc(int cpt, dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    if (cpt == 1) launch_l1s_c<REV, NC, 1>(g, lds, st, a);
-    else if (cpt == 2) launch_l1s_c<REV, NC, 2>(g, lds, st, a);
-    else launch_l1s_c<REV, NC, 4>(g, lds, st, a);
-}
-template <bool REV>
-static void launch_l1s(int nc, int cpt, dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    if (nc == 1) launch_l1s_nc<REV, 1>(cpt, g, lds, st, a);
-    else if (nc == 2) launch_l1s_nc<REV, 2>(cpt, g, lds, st, a);
-    else if (nc == 3) launch_l1s_nc<REV, 3>(cpt, g, lds, st, a);
-    else launch_l1s_nc<REV, 4>(cpt, g, lds, st, a);
-}
-template <bool REV>
-static void launch_l1(int nc, dim3 g, size_t lds, hipStream_t st, const DwtBandArgs &a) {
-    if (nc == 1) launch_l1_nc<REV, 1>(g, lds, st, a);
-    else if (nc == 2) launch_l1_nc<REV, 2>(g, lds, st, a);
-    else if (nc == 3) launch_l1_nc<REV, 3>(g, lds, st, a);
-    else launch_l1_nc<REV, 4>(g, lds, st, a);
+
+// f(std::integral_constant<int, V>) for the first V of the list that equals v
+// (the last one when none does): a run-time value picks a template argument
+template <int V0, int... Vs, typename F>
+static void with_const(int v, F f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else with_const<Vs...>(v, f);
 }
 
-// What a gfx950 workgroup can be given: 160 KiB of LDS.  A level whose band
-// of whole rows asks for no more keeps the whole-row kernels (the runtime
-// grants a launch up to the device's limit); a wider one goes to the chunked
-// instances, whose LDS does not depend on the width (static_asserts above).
-constexpr size_t kLdsPerWorkgroup = 160 * 1024;
-static bool grid_ok(dim3 g) { return g.x >= 1 && g.y >= 1 && g.y <= 65535 && g.z >= 1 && g.z <= 65535; }
-static bool refuse(const char **why, const char *msg) {
-    if (why) *why = msg;
-    return false;
+// One record of the route: its form names the kernel, the source the instance.
+template <bool REV>
+static void launch_level(const DwtLevelRoute &r, hipStream_t st, const DwtBandArgs &a, const DwtTailArgs &t) {
+    switch (r.form) {
+    case DwtForm::L1Stream: {
+        // one access per chunky pixel unless the source is planar (or smaller than an access)
+        const int px = (a.planar != 2 && a.px_fetch) ? a.bits >> 3 : 0;
+        with_const<1, 2, 3, 4>(a.nc, [&](auto NC) {
+            with_const<1, 2, 4>(r.cpt, [&](auto CPT) {
+                with_const<1, 2, 0>(px, [&](auto PX) {
+                    launch_l1s<REV, decltype(NC)::value, decltype(CPT)::value, decltype(PX)::value>(r, st, a);
+                });
+            });
+        });
+        break;
+    }
+    case DwtForm::L1Window:
+        with_const<1, 2, 3, 4>(a.nc, [&](auto NC) { launch_routed<k_dwt_l1<REV, decltype(NC)::value, kRb1>>(r, st, a); });
+        break;
+    case DwtForm::L1Chunk:
+        with_const<1, 2, 3, 4>(a.nc, [&](auto NC) { launch_routed<k_dwt_l1<REV, decltype(NC)::value, kRb1, true>>(r, st, a); });
+        break;
+    case DwtForm::BandIngest:
+        launch_routed<k_dwt_band<REV, true, kBandRb, kDwtThreads>>(r, st, a);
+        break;
+    case DwtForm::Band:
+        if (r.threads == kBandNarrow) launch_routed<k_dwt_band<REV, false, kBandRb, kBandNarrow>>(r, st, a);
+        else launch_routed<k_dwt_band<REV, false, kBandRb, kDwtThreads>>(r, st, a);
+        break;
+    case DwtForm::BandChunk:
+        launch_routed<k_dwt_band<REV, false, kBandRb, kDwtThreads, true>>(r, st, a);
+        break;
+    case DwtForm::Tail:
+        launch_routed<k_dwt_tail<REV>>(r, st, t);
+        break;
+    }
 }
 
 // Ingest + all DWT levels on `st`.  Returns false on a launch error, or
-// (*why set) without launching where a launch could not be valid.
+// (*why set) without launching anything where a launch could not be valid.
 bool launch_dwt(const DwtLaunch &p, hipStream_t st, const char **why) {
     if (why) *why = nullptr;
+    const DwtRoute route = dwt_route(p.plane_w, p.plane_h, p.nc, p.ntc, p.levels);
+    if (route.refused) {
+        if (why) *why = route.refused;
+        return false;
+    }
+    const int ll_stride = (p.plane_w + 1) / 2;
+    const size_t ll_tc = (size_t)ll_stride * ((p.plane_h + 1) / 2);
+    void *scratch[2] = {p.scratch0, p.scratch1};
     DwtBandArgs a;
     a.tif = (const uint8_t *)p.tif;
     a.strip_off = p.strip_off;
     a.rps = p.rps; a.img_w = p.img_w; a.nc = p.nc; a.bits = p.bits; a.planar = p.planar;
     a.big_endian = p.big_endian; a.mct = p.mct; a.spp_strips = p.spp_strips;
     a.ntx = p.ntx; a.tile_w = p.tile_w; a.tile_h = p.tile_h; a.row0 = p.row0;
+    a.src_stride = ll_stride;
+    a.src_tc = ll_tc;
     a.dst = p.coef;
     a.qt = p.qt;
     a.plane_w = p.plane_w;
     a.plane = (size_t)p.plane_w * p.plane_h;
+    a.ll_stride = ll_stride;
+    a.ll_tc = ll_tc;
     a.tc_w = p.tc_w; a.tc_h = p.tc_h;
     a.ragged = (p.tile_w & 15) || (p.last_tile_w & 15) || p.last_tile_w == 1;
     a.src_end = p.src_end;
     a.px_fetch = px_fetch_usable(p.src_end);
-    const int ll_stride = (p.plane_w + 1) / 2;
-    const size_t ll_tc = (size_t)ll_stride * ((p.plane_h + 1) / 2);
-    void *scratch[2] = {p.scratch0, p.scratch1};
-    for (int lv = 1; lv <= p.levels; lv++) {
-        const int maxW = (p.plane_w + (1 << (lv - 1)) - 1) >> (lv - 1);
-        const int maxH = (p.plane_h + (1 << (lv - 1)) - 1) >> (lv - 1);
-        if (lv >= 2 && ((maxW + 1) / 2) * ((maxH + 1) / 2) <= kTailLL &&
-            lds_row_stride(maxW) * maxH + kPadL + kPadR <= kTailWords) {
-            DwtTailArgs t;
-            t.src = scratch[(lv - 1) & 1];
-            t.src_stride = ll_stride;
-            t.src_tc = ll_tc;
-            t.dst = p.coef;
-            t.plane_w = p.plane_w;
-            t.plane = a.plane;
-            t.tc_w = p.tc_w; t.tc_h = p.tc_h;
-            t.level = lv; t.levels = p.levels;
-            t.qt = p.qt;
-            if (p.reversible) hipLaunchKernelGGL(k_dwt_tail<true>, dim3(p.ntc), dim3(kTailThreads), 0, st, t);
-            else hipLaunchKernelGGL(k_dwt_tail<false>, dim3(p.ntc), dim3(kTailThreads), 0, st, t);
-            return hipGetLastError() == hipSuccess;
-        }
-        const int R = kBandRb;  // kept rows per workgroup (16: 8 took 2 x 40 us for levels 2-3, 16 70 us, profiles/r04/ab_dwt_band.txt)
-        a.level = lv;
-        a.R = R;
-        a.src = scratch[(lv - 1) & 1];
-        a.src_stride = ll_stride;
-        a.src_tc = ll_tc;
-        a.ll = lv == p.levels ? nullptr : scratch[lv & 1];
-        a.ll_stride = ll_stride;
-        a.ll_tc = ll_tc;
-        const size_t lds = ((size_t)R * lds_row_stride(maxW) + kPadL + kPadR) * 4;
-        dim3 g((maxH + R - 1) / R, p.ntc);
-        // level 1: every component of a tile in one workgroup when its rows
-        // fit in LDS (each TIFF pixel read once)
-        const size_t lds1 = ((size_t)p.nc * kRb1 * lds_row_stride(maxW) + kPadL + kPadR) * 4;
-        const int cpt = maxW <= kDwtThreads ? 1 : (maxW <= 2 * kDwtThreads ? 2 : 4);
-        if (lv == 1 && lds1 <= (size_t)kDwtLdsWordsWide * 4 && maxW <= 4 * kDwtThreads) {
-            // streaming vertical pass (k_dwt_l1s), bands of kStreamBand rows,
-            // horizontal batches of 4 rows
-            a.R = JP2HIP_L1S_R;
-            const size_t lds_s =
-                ((size_t)p.nc * a.R * (kL1sSkew ? lds_row_stride_skew(maxW) : lds_row_stride(maxW)) +
-                 (kL1sSkew ? kPadLs : kPadL) + kPadR) * 4;
-            dim3 g1((maxH + kStreamBand - 1) / kStreamBand, p.ntc / p.nc);
-            if (p.reversible) launch_l1s<true>(p.nc, cpt, g1, lds_s, st, a);
-            else launch_l1s<false>(p.nc, cpt, g1, lds_s, st, a);
-        } else if (lv == 1 && lds1 <= (size_t)kDwtLdsWordsWide * 4) {
-            dim3 g1((maxH + kRb1 - 1) / kRb1, p.ntc / p.nc);
-            if (p.reversible) launch_l1<true>(p.nc, g1, lds1, st, a);
-            else launch_l1<false>(p.nc, g1, lds1, st, a);
-        } else if (lds > kLdsPerWorkgroup) {
-            // whole rows of this level do not fit in a workgroup's LDS: column
-            // chunks (level 1: every component of a tile per workgroup)
-            if (lv == 1) {
-                dim3 gc((maxH + kRb1 - 1) / kRb1, p.ntc / p.nc, dwt_chunk_count(maxW, kL1ChunkW));
-                if (!grid_ok(gc)) return refuse(why, "DWT: the tile needs more workgroups than a launch takes");
-                if (p.reversible) launch_l1_chunk<true>(p.nc, gc, st, a);
-                else launch_l1_chunk<false>(p.nc, gc, st, a);
-            } else {
-                dim3 gc(g.x, g.y, dwt_chunk_count(maxW, kBandChunkW));
-                if (!grid_ok(gc)) return refuse(why, "DWT: the tile needs more workgroups than a launch takes");
-                if (p.reversible) launch_band_chunk<true>(gc, st, a);
-                else launch_band_chunk<false>(gc, st, a);
-            }
-        } else if (lv == 1) {
-            if (p.reversible) launch_band_rb<true, true>(maxW, g, lds, st, a);
-            else launch_band_rb<false, true>(maxW, g, lds, st, a);
-        } else {
-            if (p.reversible) launch_band_rb<true, false>(maxW, g, lds, st, a);
-            else launch_band_rb<false, false>(maxW, g, lds, st, a);
-        }
+    DwtTailArgs t;
+    t.src_stride = ll_stride;
+    t.src_tc = ll_tc;
+    t.dst = p.coef;
+    t.plane_w = p.plane_w;
+    t.plane = a.plane;
+    t.tc_w = p.tc_w; t.tc_h = p.tc_h;
+    t.levels = p.levels;
+    t.qt = p.qt;
+    for (int i = 0; i < route.n; i++) {
+        const DwtLevelRoute &r = route.lv[i];
+        // level lv reads the LL level lv - 1 left in one scratch plane and leaves its own in the other
+        a.level = t.level = r.level;
+        a.src = t.src = scratch[(r.level - 1) & 1];
+        a.ll = r.level == p.levels ? nullptr : scratch[r.level & 1];
+        if (p.reversible) launch_level<true>(r, st, a, t);
+        else launch_level<false>(r, st, a, t);
         if (hipGetLastError() != hipSuccess) return false;
     }
     return true;

@@ -20,8 +20,10 @@ L1_CHUNK_W = 496    # k_dwt_l1<.., CHUNK>: level 1 with ingest
 BAND_CHUNK_W = 496  # k_dwt_band<.., CHUNK>: levels >= 2
 CHUNK_HALO = 4
 # A level keeps its whole-row kernel while 16 rows of it fit in 160 KiB of LDS
-# (csrc/dwt.hip launch_dwt): up to 2496 columns.  Tile widths that send level
-# lv -- and every level above it -- to the chunked kernels, multiples of 2^6:
+# (csrc/dwt_route.h dwt_route): up to 2496 columns.  Tile widths that send level
+# lv -- and every level above it -- to the chunked kernels, multiples of 2^6
+# (test_large_tiles.py asks dwt_route for both):
+WHOLE_ROW_MAX_W = 2496
 CHUNKED_FROM_LEVEL = {1: 4096, 2: 5120, 3: 10240}
 
 

@@ -66,6 +66,12 @@ def test_rgb8_shapes(encoder, shape, conv):
     _check(encoder, img, im.tiff_bytes(img, **kw), conv, **recipe)
 
 
+LAYOUT_SIZES = ((33, 20), (1, 3))  # width x height, the default recipe
+PLACEMENT_SIZE = (37, 21)
+# width x height, recipe overrides: the levels above the first
+LEVELS_2_UP = (200, 136, {"tile_w": 128, "tile_h": 128, "levels": 5})
+BAND_EDGES = (530, 300, {})
+
 LAYOUTS = [
     ("rgb16", {}),
     ("rgb16", {"big_endian": True}),
@@ -81,7 +87,7 @@ LAYOUTS = [
 @pytest.mark.parametrize("layout", LAYOUTS, ids=[k + "".join("_" + x for x in kw) for k, kw in LAYOUTS])
 def test_sample_layouts(encoder, layout, conv):
     kind, kw = layout
-    for w, h in ((33, 20), (1, 3)):
+    for w, h in LAYOUT_SIZES:
         img = _img(kind, w, h, seed=11)
         _check(encoder, img, im.tiff_bytes(img, rows_per_strip=7, **kw), conv)
 
@@ -93,7 +99,7 @@ def test_buffer_placement(encoder, shift, kind, conv):
     """The device buffer holds exactly the file's bytes (its last byte is the
     last pixel's last sample), or the file starts 1-3 bytes into a larger
     buffer (no pixel is aligned to its access)."""
-    img = _img(kind, 37, 21, seed=5)
+    img = _img(kind, *PLACEMENT_SIZE, seed=5)
     tif = im.tiff_bytes(img, rows_per_strip=8)
     lay, keep = jp2hip.tiff_layout(tif)
     assert lay.strip_offsets[lay.nstrips - 1] + (21 - 16) * 37 * 3 * img.dtype.itemsize == len(tif)
@@ -110,16 +116,19 @@ def test_buffer_placement(encoder, shift, kind, conv):
 def test_levels_2_up_odd_sizes(encoder, conv):
     """200 x 136 in 128^2 tiles, 5 levels: levels 2-3 (k_dwt_band) and the
     tail see odd sizes and widths that are no multiple of 16."""
-    img = _rgb8(200, 136, seed=8)
-    _check(encoder, img, im.tiff_bytes(img), conv, tile_w=128, tile_h=128, levels=5)
+    w, h, recipe = LEVELS_2_UP
+    img = _rgb8(w, h, seed=8)
+    _check(encoder, img, im.tiff_bytes(img), conv, **recipe)
 
 
 @pytest.mark.parametrize("conv", CONVS, ids=["ll", "ly"])
 def test_band_kernel_edges(encoder, conv):
     """530 x 300 in 512^2 tiles: tile widths 512 and 18, so level 2 runs
     k_dwt_band's 256-thread form and level 3 its 128-thread form (the case
-    above reaches the tail at level 2), each with a full-width tile (the
+    above reaches the tail at level 2; csrc/dwt_route.h decides, and
+    test_large_tiles.py checks that these shapes still get there), each with a full-width tile (the
     straight-line horizontal lifting), a narrow one, a first and a last band
     (windows that touch rows 0 and H-1) and a last band of fewer than 16 rows."""
-    img = _rgb8(530, 300, seed=9)
-    _check(encoder, img, im.tiff_bytes(img), conv)
+    w, h, recipe = BAND_EDGES
+    img = _rgb8(w, h, seed=9)
+    _check(encoder, img, im.tiff_bytes(img), conv, **recipe)

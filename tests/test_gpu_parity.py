@@ -52,7 +52,8 @@ CASES = [
     (150, 250, 3, 8, True, 0, 512),
     (450, 350, 3, 8, False, 2, 128),
     # tiles wider than 1024: DWT level 1 by the windowed kernel (k_dwt_l1, one
-    # component fits its LDS) or per component (k_dwt_band<INGEST>)
+    # component fits its LDS) or per component (k_dwt_band<INGEST>), as
+    # csrc/dwt_route.h decides (test_large_tiles.py checks the forms CASES reach)
     (520, 2100, 1, 8, False, 6, 2048),
     (300, 2100, 1, 16, True, 6, 2048),
     (520, 2100, 3, 8, True, 6, 2048),

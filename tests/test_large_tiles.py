@@ -2,8 +2,9 @@
 as the host decides them: the plan is built (jp2hip_packet_sequence builds
 the plan an encode builds, refusals included), 0 / 0 resolves to one tile of
 the smallest multiples of 2^levels, half-stated and negative sizes are
-refused by name, an untiled image's tile-split band is rank 0's, and the
-chunk constants the GPU cases are laid around are the header's.  No GPU."""
+refused by name, an untiled image's tile-split band is rank 0's, the chunk
+constants the GPU cases are laid around are the header's, and the DWT routes
+those cases name are the ones csrc/dwt_route.h gives them.  No GPU."""
 import os
 import re
 from ctypes import byref
@@ -13,6 +14,7 @@ import pytest
 import jp2hip
 import large_tile_cases as lt
 from jp2hip import split as js
+from test_dwt_route_host import route
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -98,3 +100,63 @@ def test_case_constants_are_the_headers():
     assert consts["kL1ChunkW"] == lt.L1_CHUNK_W
     assert consts["kBandChunkW"] == lt.BAND_CHUNK_W
     assert consts["kDwtChunkHalo"] == lt.CHUNK_HALO
+
+
+@pytest.mark.parametrize("nc", [1, 3])
+def test_chunked_from_level_is_the_routes(nc):
+    """The tile widths the chunk-edge cases use to send a level to the chunked
+    kernels (large_tile_cases.CHUNKED_FROM_LEVEL), and the widest whole-row
+    level they are laid around, as csrc/dwt_route.h routes them today."""
+    for lv, tw in lt.CHUNKED_FROM_LEVEL.items():
+        r = route(tw, 64, nc, 6)
+        assert [x["level"] for x in r[:lv + 1]] == list(range(1, lv + 2))
+        assert [x["form"] for x in r[:lv]] == ["L1Chunk"] + ["BandChunk"] * (lv - 1), (tw, r)
+        assert r[lv]["form"] == "Band" and r[lv]["gz"] == 1, (tw, r)
+    # a level the band kernel lifts -- level 2 of a one-component tile, and
+    # level 1 of a three-component one (k_dwt_band with ingest) -- on either
+    # side of the limit
+    W = lt.WHOLE_ROW_MAX_W
+    assert [x["form"] for x in route(2 * W, 64, 1, 6)[:2]] == ["L1Chunk", "Band"]
+    assert [x["form"] for x in route(2 * W + 1, 64, 1, 6)[:2]] == ["L1Chunk", "BandChunk"]
+    assert route(2 * W, 64, 1, 6)[1]["W"] == W and route(2 * W + 1, 64, 1, 6)[1]["W"] == W + 1
+    assert route(W, 64, 3, 6)[0]["form"] == "BandIngest"
+    assert route(W + 1, 64, 3, 6)[0]["form"] == "L1Chunk"
+
+
+def _corpus_tiles():
+    """(tile_w, tile_h, components, levels) of every encode of the GPU cases
+    that are laid around a DWT route: the case lists, not their fixtures."""
+    import test_gpu_dwt_fetch as tf
+    import test_gpu_parity as tp
+
+    def tile(w, h, comps, **ov):
+        rc = jp2hip.recipe(jp2hip.LOSSLESS, **ov)
+        tw, th = (rc.tile_w, rc.tile_h) if rc.tile_w else lt.resolved(w, h, rc.levels)
+        return tw, th, comps, rc.levels
+
+    out = [tile(w, h, nc, levels=levels, tile_w=t, tile_h=t) for h, w, nc, _, _, levels, t in tp.CASES]
+    out += [tile(c["w"], c["h"], c["comps"], **c["ov"]) for c in lt.NUMBERED]
+    out += [tile(c["w"], c["h"], c["comps"], **dict(c["ov"], tile_w=0, tile_h=0)) for c in lt.UNTILED]
+    out += [tile(e["w"], h, comps, **e["ov"]) for e in lt.chunk_edge_cases() for h, comps, _ in lt.CHUNK_EDGE_VARIANTS]
+    out += [tile(c["w"], c["h"], c["comps"], **c["ov"])
+            for c in (lt.gap_case(tw, comps) for tw in lt.GAP_TILE_WIDTHS for comps in lt.GAP_COMPS)]
+    out += [tile(w, h, 3, **ov) for w, h, _, ov in tf.SHAPES]
+    out += [tile(w, h, 4 if kind == "rgba8" else 1 if kind.startswith("gray") else 3)
+            for kind, _ in tf.LAYOUTS for w, h in tf.LAYOUT_SIZES]
+    out += [tile(*tf.PLACEMENT_SIZE, 3), tile(tf.LEVELS_2_UP[0], tf.LEVELS_2_UP[1], 3, **tf.LEVELS_2_UP[2]),
+            tile(tf.BAND_EDGES[0], tf.BAND_EDGES[1], 3, **tf.BAND_EDGES[2])]
+    return sorted(set(out))
+
+
+def test_gpu_corpus_reaches_every_dwt_form():
+    """The byte-identity cases of test_gpu_parity, test_gpu_large_tiles and
+    test_gpu_dwt_fetch between them launch every kernel form of dwt.hip:
+    a retuned limit in csrc/dwt_route.h that takes one away fails here."""
+    seen = set()
+    for tw, th, nc, levels in _corpus_tiles():
+        for x in route(tw, th, nc, levels):
+            seen.add((x["form"], x["cpt"] if x["form"] == "L1Stream" else x["threads"] if x["form"] == "Band" else 0))
+    want = {("L1Stream", 1), ("L1Stream", 2), ("L1Stream", 4), ("L1Window", 0), ("L1Chunk", 0), ("BandIngest", 0),
+            ("Band", 128), ("Band", 256), ("BandChunk", 0), ("Tail", 0)}
+    assert want - seen == set(), sorted(seen)
+    assert seen - want == set(), sorted(seen)
