@@ -109,6 +109,13 @@ typedef struct jp2hip_recipe {
                              /* (test.jpx's order); <= 0: tile after tile      */
 } jp2hip_recipe;
 
+/* Code-stream organisation that is no part of the coding recipe (Kakadu's ORG
+ * cluster; ORGgen_plt / ORGtparts keep living in the recipe). All zero = as before. */
+typedef struct jp2hip_organisation {
+    int32_t tlm;          /* ORGgen_tlm: 1 = TLM marker segments in the main header */
+    int32_t reserved[3];  /* 0 */
+} jp2hip_organisation;
+
 #define JP2HIP_PHOTO_DEFAULT 0       /* BlackIsZero grey / RGB, by component count */
 #define JP2HIP_PHOTO_WHITE_IS_ZERO 1 /* grey, 0 = white (bits 1, 2, 4 only)        */
 #define JP2HIP_PHOTO_PALETTE 2       /* indices into `colormap` (bits 1, 2, 4, 8)  */
@@ -265,6 +272,30 @@ int64_t jp2hip_device_bytes(jp2hip_ctx *ctx);
  * 30 s) for busy ones to become idle before it fails.
  * Returns 0, or < 0 for a null context. */
 int jp2hip_set_memory_limits(jp2hip_ctx *ctx, int64_t soft, int64_t hard);
+
+/* The organisation of every later encode on ctx, its tile-split peers included
+ * (peers added later inherit it).  NULL = all zero.  With tlm = 1 the main
+ * header ends in TLM marker segments (ISO/IEC 15444-1 A.7.1; Stlm 0x60: 16-bit
+ * Ttlm, 32-bit Ptlm) that list every tile-part's tile index and length in the
+ * order the tile-parts lie in the file, so a reader finds any tile-part from
+ * one read of the header; their T = 6 * tile-parts + 6 * segments bytes count
+ * in the jp2c box length, stats.out_bytes, a split's file_len / file_offset
+ * and Kdu-Layer-Info's L(bytes).  A rate-driven encode with a TLM is the
+ * encode without one whose byte target is T lower (floored at 0): the TLM is
+ * part of the code-stream the target bounds.  A tile-split over a caller's
+ * callback is collective in the organisation as it is in the recipe: every
+ * rank sets the same one.  Not to be called while ctx is encoding.  Returns
+ * 0, or < 0 with a message that names the field (tlm other than 0 / 1,
+ * reserved non-zero). */
+int jp2hip_set_organisation(jp2hip_ctx *ctx, const jp2hip_organisation *org);
+
+/* Host-only, exported for tests (like jp2hip_packet_sequence): the TLM marker
+ * segments for n tile-parts in file order -- per segment FF55, Ltlm = 4 + 6 k,
+ * Ztlm 0, 1, ..., Stlm 0x60, then k <= 10921 pairs (tiles[i], lengths[i]),
+ * big-endian.  Returns their byte count and writes them when cap suffices;
+ * < 0 on a null argument or more tile-parts than 256 segments hold. */
+int64_t jp2hip_tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n,
+                            uint8_t *dst, size_t cap);
 
 /* Which SDMA engines the code-stream copies use, per GPU probed so far, and
  * every engine's measured device -> host rate ("" before the first encode):
@@ -492,6 +523,9 @@ typedef struct jp2hip_batch_result {
 
 int jp2hip_batch_create(jp2hip_batch **out, const jp2hip_batch_config *cfg, jp2hip_upload_fn upload,
                         void *user);
+/* jp2hip_set_organisation on every context of the queue; before the first
+ * submit (< 0 after it, or for a refused organisation). */
+int jp2hip_batch_set_organisation(jp2hip_batch *b, const jp2hip_organisation *org);
 /* Queue one image: convert `tiff_path` into `jpx_path` (written atomically)
  * with `conversion` (recipe NULL -> Bucketeer recipe), then upload it under
  * `image_id`.  Never blocks on the GPU; returns < 0 after close. */

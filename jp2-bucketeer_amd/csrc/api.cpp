@@ -247,6 +247,30 @@ int jp2hip_set_memory_limits(jp2hip_ctx *ctx, int64_t soft, int64_t hard) {
     return 0;
 }
 
+int jp2hip_set_organisation(jp2hip_ctx *ctx, const jp2hip_organisation *org) {
+    jp2hip_organisation o;
+    std::memset(&o, 0, sizeof o);
+    if (org) o = *org;
+    if (o.tlm != 0 && o.tlm != 1) return fail("organisation: tlm must be 0 or 1, not " + std::to_string(o.tlm));
+    for (int32_t r : o.reserved)
+        if (r != 0) return fail("organisation: reserved must be 0");
+    if (!ctx) return fail("null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->org = o;
+    for (jp2hip_ctx *p : ctx->peers)
+        if (jp2hip_set_organisation(p, &o) != 0) return -1;
+    return 0;
+}
+
+int64_t jp2hip_tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n, uint8_t *dst, size_t cap) {
+    if (!tiles || !lengths || n < 0) return fail("null tiles or lengths, or a negative count");
+    if (n > jp2hip::kTlmMaxEntries)
+        return fail("more tile-parts than 256 TLM marker segments hold (" + std::to_string(jp2hip::kTlmMaxEntries) + ")");
+    const int64_t bytes = jp2hip::tlm_bytes(n);
+    if (dst && cap >= (size_t)bytes) jp2hip::tlm_segments(tiles, lengths, n, dst);
+    return bytes;
+}
+
 const char *jp2hip_dma_engines(void) {
     thread_local std::string s;
     s = jp2hip::dma_engine_report();
@@ -426,6 +450,7 @@ int jp2hip_split_peers(jp2hip_ctx *ctx, const int32_t *ordinals, int32_t n, int6
             for (jp2hip_ctx *q : made) jp2hip_destroy(q);
             return fail(e);
         }
+        p->org = ctx->org;  // (jp2hip_set_organisation: peers added later inherit it)
         made.push_back(p);
     }
     for (jp2hip_ctx *p : ctx->peers) jp2hip_destroy(p);

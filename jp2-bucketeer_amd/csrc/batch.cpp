@@ -133,7 +133,7 @@ struct jp2hip_batch {
     std::condition_variable res_cv;
     std::deque<jp2hip_batch_result> results;
     std::atomic<int64_t> pending{0};
-    std::atomic<bool> closed{false};
+    std::atomic<bool> closed{false}, submitted_any{false};
     std::atomic<int> readers_left{0}, encoders_left{0};
 
     void finish(Job &j) {
@@ -323,9 +323,17 @@ int jp2hip_batch_create(jp2hip_batch **out, const jp2hip_batch_config *cfg, jp2h
     return 0;
 }
 
+int jp2hip_batch_set_organisation(jp2hip_batch *b, const jp2hip_organisation *org) {
+    if (!b || b->submitted_any) return -1;  // (its encoders are idle before the first submit)
+    for (jp2hip_ctx *c : b->ctxs)
+        if (jp2hip_set_organisation(c, org) != 0) return -1;  // jp2hip_last_error() holds the reason
+    return 0;
+}
+
 int jp2hip_batch_submit(jp2hip_batch *b, int64_t job, const char *image_id, const char *tiff_path,
                         const char *jpx_path, int conversion, const jp2hip_recipe *recipe) {
     if (!b || !image_id || !tiff_path || !jpx_path || b->closed) return -1;
+    b->submitted_any = true;
     Job j;
     j.job = job;
     j.id = image_id;

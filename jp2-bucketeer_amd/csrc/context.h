@@ -34,6 +34,10 @@ struct jp2hip_ctx {
     jp2hip_config cfg;
     int threads = 1;
     PlanCache pc;
+    // jp2hip_set_organisation: read by every encode, no part of the plan
+    // cache's key (the plan, its tables and the main header up to the TLM
+    // are the same with and without it)
+    jp2hip_organisation org{};
     // tile-split members (jp2hip_split_peers): images of at least
     // split_min_pixels are encoded by this context (rank 0) and these
     // (ranks 1..), owned here

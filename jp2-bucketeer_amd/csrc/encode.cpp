@@ -63,12 +63,16 @@ namespace {
 // A rate-driven encode's target (bytes): the floor(rate * W * H / 8) the
 // oracle's predict_and_code uses; slope prediction's is the same, -1 = off
 // (an image so small that the target is 0 bytes still predicts, as the
-// oracle does: 0 is a target like any other).
-int64_t rate_target_of(const jp2hip_recipe &rc, int w, int h) {
-    return (int64_t)std::floor(rc.rate_bpp * (double)w * (double)h / 8.0);
+// oracle does: 0 is a target like any other).  tlm: the bytes of the TLM marker
+// segments, part of the code-stream the target bounds -- a rate-driven encode
+// with a TLM is the encode without one whose target is that much lower
+// (floored at 0), so everything the target steers sees the lower one.
+int64_t rate_target_of(const jp2hip_recipe &rc, int w, int h, int64_t tlm) {
+    const int64_t target = (int64_t)std::floor(rc.rate_bpp * (double)w * (double)h / 8.0);
+    return tlm ? std::max<int64_t>(0, target - tlm) : target;
 }
-int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h) {
-    return rc.slope_skip && rc.rate_bpp > 0.0 ? rate_target_of(rc, w, h) : -1;
+int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h, int64_t tlm) {
+    return rc.slope_skip && rc.rate_bpp > 0.0 ? rate_target_of(rc, w, h, tlm) : -1;
 }
 // The rate loop's first budget: its header estimate (16 bytes per packet)
 // lands the usual encode under the target (C2: 8 985 521 of 9 000 000 bytes).
@@ -104,10 +108,13 @@ int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conv
 struct FilePart {
     const Plan &file, &coded;  // names the file (the plan / a split's full plan); was coded here (the plan / sub)
     bool with_main, with_eoc, have;
-    size_t fh = 0, head = 0, bytes = 0;  // file header; through the main header; the whole part
-    void size(const SourceMeta &meta, size_t mh_bytes, int64_t part_bytes) {
+    size_t fh = 0, head = 0, bytes = 0;  // file header; through the main header (its TLM included); the whole part
+    size_t tlm = 0;                      // the TLM marker segments that end the main header (with_main)
+    const uint8_t *tlm_host = nullptr;   // ... written on the host (a split's rank 0); null: by the device
+    void size(const SourceMeta &meta, size_t mh_bytes, int64_t part_bytes, size_t tlm_segs) {
         fh = with_main ? file_header_bytes(file, meta) : 0;
-        head = with_main ? fh + mh_bytes : 0;
+        tlm = with_main ? tlm_segs : 0;
+        head = with_main ? fh + mh_bytes + tlm : 0;
         bytes = head + (size_t)(have ? part_bytes : 0) + (with_eoc ? 2 : 0);
     }
 };
@@ -135,9 +142,12 @@ int finish_part(jp2hip_ctx *ctx, const FilePart &fp, const SourceMeta &meta, std
         main_header(P, mh, K.data(), layer_end.data());
         write_file_header(P, meta, (uint64_t)cs_bytes, buf);
         std::memcpy(buf + fp.fh, mh.data(), mh.size());
+        if (fp.tlm_host) std::memcpy(buf + fp.head - fp.tlm, fp.tlm_host, fp.tlm);
     }
     const bool prof = ctx->cfg.profile != 0;
-    if (fp.have && (!ctx->gpu.t2_emit(fp.coded, 0, (uint64_t)sum.part_bytes, buf + fp.head, prof, st, err) ||
+    // the device writes the TLM segments in front of its tile-parts: one copy brings both
+    const size_t dev_tlm = fp.tlm_host ? 0 : fp.tlm;
+    if (fp.have && (!ctx->gpu.t2_emit(fp.coded, dev_tlm, (uint64_t)sum.part_bytes, buf + fp.head - dev_tlm, prof, st, err) ||
                     !ctx->gpu.collect_profile(st, err))) {
         out_free(buf);
         return fail(err);
@@ -212,7 +222,11 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     const Plan &plan = pc.plan;
     const bool prof = ctx->cfg.profile != 0;
     StageTimes st;
-    int64_t skip_target = skip_target_of(rc, plan.w, plan.h);
+    // the organisation is no part of the cached plan: its bytes come from the tile-part count alone
+    const int64_t tlm = ctx->org.tlm ? tlm_bytes((int64_t)pc.tabs.tp.size()) : 0;
+    if (ctx->org.tlm && (int64_t)pc.tabs.tp.size() > kTlmMaxEntries)
+        return fail("tlm: more tile-parts than 256 TLM marker segments hold");
+    int64_t skip_target = skip_target_of(rc, plan.w, plan.h, tlm);
     // tier-2 tables first: every host->device copy of the encode is issued
     // while the stream is idle (a copy queued behind kernels holds up the
     // copy engine for the other contexts)
@@ -240,7 +254,7 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         }
         if (sum.err) return fail("tier-1 output capacity exceeded");
         iters = 1;
-        cs_bytes = (int64_t)mh_bytes + sum.part_bytes + 2;
+        cs_bytes = (int64_t)mh_bytes + tlm + sum.part_bytes + 2;
     } else {
         // the rate loop runs on the device (GpuEncoder::rate_loop): one
         // iteration per host wait, what the usual encode needs (its first
@@ -248,7 +262,7 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         // heavier takes a second wait for its next iterations
         RateState init;
         std::memset(&init, 0, sizeof init);
-        init.target = rate_target_of(rc, plan.w, plan.h);
+        init.target = rate_target_of(rc, plan.w, plan.h, tlm);
         init.budget = first_budget_of(plan, init.target);
         init.fixed = (int64_t)mh_bytes + 2;
         init.skip_target = skip_target;
@@ -278,10 +292,10 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
             if (rs.halt) break;
         }
         iters = rs.iters;
-        cs_bytes = rs.cs_bytes;  // (= init.fixed + sum.part_bytes: device_common.h rate_step)
+        cs_bytes = rs.cs_bytes + tlm;  // (= init.fixed + sum.part_bytes: device_common.h rate_step)
     }
     FilePart fp{plan, plan, true, true, true};
-    fp.size(meta, mh_bytes, sum.part_bytes);
+    fp.size(meta, mh_bytes, sum.part_bytes, (size_t)tlm);
     uint8_t *buf = out_alloc(fp.bytes);
     if (!buf) return fail("out of (pinned) host memory");
     if (finish_part(ctx, fp, meta, std::vector<uint64_t>(sum.kc, sum.kc + rc.layers), sum.tp_hdr_bytes,
@@ -352,10 +366,16 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     StageTimes st;
     std::vector<uint64_t> keys;
     std::vector<int64_t> cum;
+    // TLM (collective, like the recipe: every rank's context has the same
+    // organisation): its bytes are known from the full plan alone (so a plan
+    // with too many tile-parts fails every rank here, before any exchange)
+    const int64_t ntp_full = ctx->org.tlm ? tile_parts_in(full, 0, full.ntx * full.nty) : 0;
+    if (ntp_full > kTlmMaxEntries) return fail("tlm: more tile-parts than 256 TLM marker segments hold");
+    const int64_t tlm = tlm_bytes(ntp_full);
     // slope prediction over the whole image: the plane histogram is summed
     // over ranks (one all-reduce of kSlopeBins + 1 int64, the last a failure
     // flag, so a rank that failed earlier still joins the exchange)
-    int64_t skip_target = skip_target_of(rc, full.w, full.h);
+    int64_t skip_target = skip_target_of(rc, full.w, full.h, tlm);
     bool hist_done = false;
     GpuEncoder::HistReduce reduce = [&](std::vector<int64_t> &h) {
         hist_done = true;
@@ -445,7 +465,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         ok = ok && (!have || ctx->gpu.segments(sub, keys, cum, err));
         std::vector<int64_t> flag(1);
         if (!exchange(flag, 0, ok) || !ok) return fail(err);
-        const int64_t target = rate_target_of(rc, full.w, full.h);
+        const int64_t target = rate_target_of(rc, full.w, full.h, tlm);  // (cs_bytes: without the TLM, as the target)
         int64_t budget = first_budget_of(full, target);
         bool rerun = false;
         for (int it = 0; it < 8; it++) {
@@ -469,11 +489,22 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // error in the emission itself, after the exchange, fails this rank
     // alone: the caller treats any rank's failure as the encode's (jp2hip.h)
     FilePart fp{full, sub, rank == 0, rank == world - 1, have};
-    fp.size(meta, mh.size(), sum.part_bytes);
+    fp.size(meta, mh.size(), sum.part_bytes, (size_t)tlm);
     uint8_t *buf = out_alloc(fp.bytes);
     bool ready = buf != nullptr;
     if (!ready) err = "out of (pinned) host memory";
     if (ready && have) ready = ctx->gpu.t2_reserve(sum.part_bytes, err);
+    // TLM: this rank's tile-part lengths (Psot, file order) come off the
+    // device before the exchange below, which carries the failure of a rank
+    // that could not read them
+    std::vector<uint32_t> tp_len;
+    if (ready && have && tlm) {
+        ready = ctx->gpu.t2_tp_lengths(tp_len, err);
+        if (ready && (int64_t)tp_len.size() != tile_parts_in(full, tile0, tile1)) {
+            ready = false;
+            err = "tlm: the band's tile-part count differs from its plan's";
+        }
+    }
     std::vector<int64_t> sizes((size_t)world + 1, 0);
     sizes[rank] = (int64_t)fp.bytes;
     if (!exchange(sizes, (size_t)world, ready) || !ready) {
@@ -485,6 +516,33 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         if (r < rank) off += (uint64_t)sizes[r];
         flen += (uint64_t)sizes[r];
     }
+    // TLM: rank 0 owns the main header, so the ranks sum their lengths into
+    // the file-order vector -- a rank's tile-parts are one contiguous run of
+    // it (whole flush stripes, after those of the tiles before its band), the
+    // other ranks add zeros -- kTlmChunk entries an exchange; every rank joins
+    // every chunk, one with an empty band too.  Rank 0 then writes the
+    // segments on the host with the function jp2hip_tlm_segments exports.
+    std::vector<uint8_t> tlm_seg;
+    if (tlm) {
+        constexpr int64_t kTlmChunk = 1024;
+        std::vector<int64_t> all((size_t)ntp_full, 0);
+        const int64_t first = tile_parts_in(full, 0, tile0);
+        for (size_t i = 0; i < tp_len.size(); i++) all[(size_t)first + i] = (int64_t)tp_len[i];
+        for (int64_t c0 = 0; c0 < ntp_full; c0 += kTlmChunk)
+            if (!allreduce(all.data() + c0, (int)std::min(kTlmChunk, ntp_full - c0))) {
+                out_free(buf);
+                return fail("split: all-reduce failed");
+            }
+        if (rank == 0) {
+            std::vector<uint16_t> tiles;
+            tile_part_order(full, 0, full.ntx * full.nty, tiles);
+            std::vector<uint32_t> lens(all.begin(), all.end());
+            tlm_seg.resize((size_t)tlm);
+            tlm_segments(tiles.data(), lens.data(), ntp_full, tlm_seg.data());
+            fp.tlm_host = tlm_seg.data();
+        }
+    }
+    cs_bytes += tlm;
     if (finish_part(ctx, fp, meta, K, g_tp_hdr, g_layer.data(), cs_bytes, sum, buf, st, out, out_len, stats, t_start,
                     0.0, (int64_t)flen, iters))
         return -1;

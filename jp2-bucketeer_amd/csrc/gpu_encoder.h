@@ -167,9 +167,15 @@ class GpuEncoder {
     // the device code-stream buffer t2_emit writes, sized for part_bytes
     // (t2_emit reserves it too; the split path reserves before its exchange)
     bool t2_reserve(uint64_t part_bytes, std::string &err);
-    // host_dst must be pinned (hipHostMalloc) memory
-    bool t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, uint8_t *host_dst, bool profile,
+    // host_dst must be pinned (hipHostMalloc) memory.  tlm_bytes > 0: the
+    // TLM marker segments of the part's tile-parts (k_t2_tlm; tlm_bytes is
+    // jp2hip::tlm_bytes of their count) are written in front of them, and
+    // host_dst receives tlm_bytes + part_bytes in the one copy
+    bool t2_emit(const Plan &plan, uint64_t tlm_bytes, uint64_t part_bytes, uint8_t *host_dst, bool profile,
                  StageTimes &st, std::string &err);
+    // the tile-part lengths (Psot) of the last sizing pass, in the part's
+    // stream order (one host wait; the split's TLM exchange)
+    bool t2_tp_lengths(std::vector<uint32_t> &lengths, std::string &err);
     // stage times of the last encode from its events (profile mode; call
     // after the encode's last host wait)
     bool collect_profile(StageTimes &st, std::string &err);

@@ -204,6 +204,26 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T);
 // component) order.  RPCL gives the identity.  A tile-part per resolution
 // (RLCP, RPCL) takes its packets as a contiguous run of this sequence.
 void packet_sequence(const Plan &P, int t, std::vector<uint32_t> &seq);
+// TLM marker segments (A.7.1, jp2hip_set_organisation): an entry per
+// tile-part in file order (the order of T2Tables::tp), at most kTlmSegEntries
+// to a segment (Ltlm is 16 bits: 4 + 6 * 10921 = 65530), Ztlm up to 255.
+constexpr int kTlmSegEntries = 10921;
+constexpr int64_t kTlmMaxEntries = (int64_t)256 * kTlmSegEntries;
+constexpr int64_t kTlmSegBytes = 6 + 6 * (int64_t)kTlmSegEntries;  // a full segment
+// The segments' byte count for ntp tile-parts: 6 an entry, 6 a segment.
+int64_t tlm_bytes(int64_t ntp);
+// Writes them (tlm_bytes(n) bytes) on the host: the split's rank 0, and
+// jp2hip_tlm_segments; the single-GPU encode writes the same bytes on the
+// device (t2_device.hip k_t2_tlm).
+void tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n, uint8_t *dst);
+// Tile-parts of tile t (one per non-empty resolution with tparts_r, else one),
+// of tiles [tile0, tile1), and the tile of each of their tile-parts in file
+// order -- T2Tables::tp's order and count without the precinct tables.
+// (Plan::ntileparts is the rate loop's header estimate: it counts a tile-part
+// per resolution whatever tparts_r says.)
+int tile_part_count(const Plan &P, int t);
+int64_t tile_parts_in(const Plan &P, int tile0, int tile1);
+void tile_part_order(const Plan &P, int tile0, int tile1, std::vector<uint16_t> &tiles);
 // What the host reads back after a tier-2 sizing pass (one D2H per pass).
 struct T2Summary {
     int64_t part_bytes;               // tile-parts of the tiles coded (SOT .. last packet)

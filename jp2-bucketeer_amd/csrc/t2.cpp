@@ -270,6 +270,57 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
     }
 }
 
+// ---- TLM marker segments (A.7.1; jp2hip_set_organisation) ----
+
+int tile_part_count(const Plan &P, int t) {
+    int n = 0;
+    for (int r = 0; r <= P.rc.levels; r++) {
+        const Resolution &R0 = P.tiles[(size_t)t].tc[0].res[r];
+        if (R0.npx * R0.npy) n++;
+    }
+    return P.rc.tparts_r ? n : std::min(n, 1);
+}
+
+int64_t tile_parts_in(const Plan &P, int tile0, int tile1) {
+    int64_t n = 0;
+    for (int t = tile0; t < tile1; t++) n += tile_part_count(P, t);
+    return n;
+}
+
+void tile_part_order(const Plan &P, int tile0, int tile1, std::vector<uint16_t> &tiles) {
+    tiles.clear();
+    std::vector<int> count((size_t)std::max(0, tile1 - tile0));
+    for (int t = tile0; t < tile1; t++) count[(size_t)(t - tile0)] = tile_part_count(P, t);
+    const std::vector<int> ends = flush_stripe_ends(P.nty, P.rc.tile_h, P.h, P.rc.flush_period);
+    int ty0 = 0;
+    for (int e : ends) {  // (the loop t2_tables orders T.tp with)
+        const int a = std::max(tile0, ty0 * P.ntx), b = std::min(tile1, e * P.ntx);
+        for (int k = 0; k <= P.rc.levels; k++)
+            for (int t = a; t < b; t++)
+                if (k < count[(size_t)(t - tile0)]) tiles.push_back((uint16_t)t);
+        ty0 = e;
+    }
+}
+
+int64_t tlm_bytes(int64_t ntp) {
+    return ntp > 0 ? 6 * ntp + 6 * ((ntp + kTlmSegEntries - 1) / kTlmSegEntries) : 0;
+}
+
+void tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n, uint8_t *dst) {
+    for (int64_t i0 = 0, z = 0; i0 < n; i0 += kTlmSegEntries, z++) {
+        const int64_t k = std::min<int64_t>(kTlmSegEntries, n - i0);
+        dst[0] = 0xFF; dst[1] = 0x55;
+        be16(dst + 2, (uint32_t)(4 + 6 * k));
+        dst[4] = (uint8_t)z;
+        dst[5] = 0x60;  // Stlm: ST = 2 (16-bit Ttlm), SP = 1 (32-bit Ptlm)
+        dst += 6;
+        for (int64_t i = i0; i < i0 + k; i++, dst += 6) {
+            be16(dst, tiles[i]);
+            be32(dst + 2, lengths[i]);
+        }
+    }
+}
+
 // ---- the boxes in front of the code-stream ----
 // What the source states about its pixels goes into jp2h (DESIGN.md "Source
 // metadata"): its ICC profile into colr, its ExtraSamples into cdef, its

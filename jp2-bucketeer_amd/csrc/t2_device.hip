@@ -22,6 +22,7 @@
 //   k_t2_tp_emit      SOT + PLT + SOD, packet offsets                  (final pass)
 //   k_t2_wave<true>   SOP + header + EPH, body offsets                 (final pass)
 //   k_t2_copy         code-block bytes into the bodies                 (final pass)
+//   k_t2_tlm          TLM marker segments in front of the tile-parts   (final pass, jp2hip_set_organisation)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -979,6 +980,32 @@ __global__ void __launch_bounds__(64) k_t2_tp_emit(T2Args a) {
     else tpart_emit<false>(a, t);
 }
 
+// TLM marker segments (A.7.1; jp2hip_internal.h tlm_segments writes the same
+// bytes on the host) at the start of `out`, in front of the tile-parts (which
+// start at a.base = the segments' byte count): a thread per tile-part writes
+// its entry -- Ttlm = the tile index, Ptlm = Psot, in the stream order
+// k_t2_total left tp_len in -- and the first entry's thread of a segment its
+// header.  Every field lies on an even offset of the buffer, so it goes out
+// as big-endian 16-bit halves, three stores an entry.
+__global__ void __launch_bounds__(256) k_t2_tlm(T2Args a) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.ntp) return;
+    const int z = t / kTlmSegEntries, j = t - z * kTlmSegEntries;
+    auto be = [](uint32_t v) { return (uint16_t)(((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu)); };
+    uint16_t *seg = (uint16_t *)(a.out + (size_t)z * kTlmSegBytes);
+    if (j == 0) {
+        const int k = min(kTlmSegEntries, a.ntp - z * kTlmSegEntries);
+        seg[0] = be(0xFF55u);
+        seg[1] = be((uint32_t)(4 + 6 * k));
+        seg[2] = be(((uint32_t)z << 8) | 0x60u);  // Ztlm, Stlm: 16-bit Ttlm, 32-bit Ptlm
+    }
+    const uint32_t len = a.tp_len[t];
+    uint16_t *e = seg + 3 + 3 * j;
+    e[0] = be((uint32_t)a.tps[t].tile);
+    e[1] = be(len >> 16);
+    e[2] = be(len & 0xFFFFu);
+}
+
 // code-block bytes into the packet bodies: one wave per block, its layer
 // pieces in turn; bytes move in 16-byte vector loads/stores where source and
 // destination are both aligned, else one byte per lane
@@ -1386,14 +1413,30 @@ bool GpuEncoder::t2_reserve(uint64_t part_bytes, std::string &err) {
     return ensure<uint8_t>(t2out, part_bytes, err);
 }
 
-bool GpuEncoder::t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, uint8_t *host_dst, bool profile,
+bool GpuEncoder::t2_tp_lengths(std::vector<uint32_t> &lengths, std::string &err) {
+    HIPCHECK(hipSetDevice(device));
+    lengths.assign((size_t)t2_ntp, 0);
+    if (!t2_ntp) return true;
+    HIPCHECK(hipMemcpyAsync(lengths.data(), t2tplen.ptr, sizeof(uint32_t) * (size_t)t2_ntp, hipMemcpyDeviceToHost,
+                            stream));
+    return host_wait(err);
+}
+
+bool GpuEncoder::t2_emit(const Plan &plan, uint64_t tlm_bytes, uint64_t part_bytes, uint8_t *host_dst, bool profile,
                          StageTimes &st, std::string &err) {
     HIPCHECK(hipSetDevice(device));
     const int nb = (int)plan.blocks.size();
+    // the part starts with its TLM segments (none: 0 bytes), the tile-parts follow at `base`
+    const uint64_t base = tlm_bytes;
+    if (tlm_bytes && tlm_bytes != (uint64_t)jp2hip::tlm_bytes(t2_ntp)) {
+        err = "t2_emit: the TLM byte count is not that of the part's tile-parts";
+        return false;
+    }
     if (!ensure<uint8_t>(t2out, base + part_bytes, err)) return false;
     T2Args a = t2_args(plan);
     a.base = base;
     HIPCHECK(hipEventRecord(ev[kEvT2Begin], stream));
+    if (tlm_bytes) hipLaunchKernelGGL(k_t2_tlm, dim3((t2_ntp + 255) / 256), dim3(256), 0, stream, a);
     if (t2_ntp) hipLaunchKernelGGL(k_t2_tp_emit, dim3((t2_ntp + 63) / 64), dim3(64), 0, stream, a);
     if (t2_nprec && t2_wave)
         hipLaunchKernelGGL(k_t2_wave<true>, dim3((t2_nprec + kT2Waves - 1) / kT2Waves), dim3(64 * kT2Waves),
@@ -1411,7 +1454,7 @@ bool GpuEncoder::t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, u
     if (part_bytes) {
         // on a DMA engine, released by the stream (dma_to_host): no blit
         // kernel competes with the other contexts' kernels for CUs
-        if (!dma_to_host(host_dst, (const uint8_t *)t2out.ptr + base, part_bytes, err)) return false;
+        if (!dma_to_host(host_dst, (const uint8_t *)t2out.ptr, base + part_bytes, err)) return false;
         HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
         if (profile && !host_wait(err)) return false;  // (the events below must be complete)
     } else {
@@ -1420,7 +1463,7 @@ bool GpuEncoder::t2_emit(const Plan &plan, uint64_t base, uint64_t part_bytes, u
     }
 #else  // A/B builds: the HIP runtime's copy (a blit kernel for pinned memory)
     if (part_bytes)
-        HIPCHECK(hipMemcpyAsync(host_dst, (const uint8_t *)t2out.ptr + base, part_bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHECK(hipMemcpyAsync(host_dst, (const uint8_t *)t2out.ptr, base + part_bytes, hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipEventRecord(ev[kEvT2End], stream));
     if (!host_wait(err)) return false;
 #endif

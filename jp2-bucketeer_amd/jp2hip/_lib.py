@@ -45,6 +45,12 @@ class Recipe(Structure):
                 ("flush_period", c_int32)]
 
 
+class Organisation(Structure):
+    """jp2hip_organisation: code-stream organisation that is no part of the
+    recipe (Kakadu's ORG cluster).  All zero = none."""
+    _fields_ = [("tlm", c_int32), ("reserved", c_int32 * 3)]
+
+
 class Layout(Structure):
     _fields_ = [("width", c_int32), ("height", c_int32), ("components", c_int32),
                 ("bits", c_int32), ("planar", c_int32), ("big_endian", c_int32),
@@ -132,6 +138,8 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            "jp2hip_split_peers", "jp2hip_tiff_pixels", "jp2hip_env_check",
            # the progression order's packet sequence (api.cpp; host only)
            "jp2hip_packet_sequence",
+           # code-stream organisation: TLM marker segments (api.cpp, batch.cpp; jp2hip_tlm_segments host only)
+           "jp2hip_set_organisation", "jp2hip_batch_set_organisation", "jp2hip_tlm_segments",
            # device-memory policy (api.cpp; csrc/context.h EncodeEnd)
            "jp2hip_device_bytes", "jp2hip_set_memory_limits", "jp2hip_device_memory", "jp2hip_dma_engines")
 
@@ -194,6 +202,10 @@ def lib():
     L.jp2hip_packet_sequence.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(Recipe), c_int32,
                                          POINTER(c_uint32), c_int64]
     L.jp2hip_packet_sequence.restype = c_int64
+    L.jp2hip_set_organisation.argtypes = [c_void_p, POINTER(Organisation)]
+    L.jp2hip_batch_set_organisation.argtypes = [c_void_p, POINTER(Organisation)]
+    L.jp2hip_tlm_segments.argtypes = [POINTER(ctypes.c_uint16), POINTER(c_uint32), c_int64, c_void_p, c_size_t]
+    L.jp2hip_tlm_segments.restype = c_int64
     L.jp2hip_device_bytes.argtypes = [c_void_p]
     L.jp2hip_device_bytes.restype = c_int64
     L.jp2hip_set_memory_limits.argtypes = [c_void_p, c_int64, c_int64]
@@ -297,6 +309,24 @@ def packet_sequence(width: int, height: int, components: int, bits: int, rcp: Re
     if int(lib().jp2hip_packet_sequence(width, height, components, bits, byref(rcp), tile, buf, n)) != n:
         raise Jp2hipError(last_error())
     return list(buf[:n])
+
+
+def tlm_segments(tiles, lengths) -> bytes:
+    """The TLM marker segments (jp2hip_tlm_segments; no GPU) for tile-parts
+    in file order: ``tiles[i]`` the tile index and ``lengths[i]`` the length
+    (Psot) of the i-th.  Raises for more tile-parts than 256 segments hold."""
+    n = len(tiles)
+    if len(lengths) != n:
+        raise ValueError("tiles and lengths differ in length")
+    t = (ctypes.c_uint16 * max(1, n))(*tiles)
+    ln = (c_uint32 * max(1, n))(*lengths)
+    need = int(lib().jp2hip_tlm_segments(t, ln, n, None, 0))
+    if need < 0:
+        raise Jp2hipError(last_error())
+    out = ctypes.create_string_buffer(max(1, need))
+    if int(lib().jp2hip_tlm_segments(t, ln, n, out, need)) != need:
+        raise Jp2hipError(last_error())
+    return out.raw[:need]
 
 
 def tiff_layout(data: bytes):
@@ -425,6 +455,14 @@ class Encoder:
     def set_memory_limits(self, soft: int = 0, hard: int = 0):
         """jp2hip_set_memory_limits: <= 0 keeps the default of each."""
         if lib().jp2hip_set_memory_limits(self._h, int(soft), int(hard)) != 0:
+            raise Jp2hipError(last_error())
+
+    def set_organisation(self, tlm: bool | int = 0, reserved=(0, 0, 0)):
+        """jp2hip_set_organisation, for every later encode on this context and
+        its tile-split peers: ``tlm`` = TLM marker segments in the main header
+        (ORGgen_tlm).  Not while the context is encoding."""
+        org = Organisation(int(tlm), (c_int32 * 3)(*reserved))
+        if lib().jp2hip_set_organisation(self._h, byref(org)) != 0:
             raise Jp2hipError(last_error())
 
     def _take(self, out, n, copy=True):

@@ -63,7 +63,7 @@ class BatchResult(Structure):
 UPLOAD_FN = CFUNCTYPE(c_int, c_void_p, c_char_p, c_char_p)
 
 BATCH_EXPORTS = ("jp2hip_batch_create", "jp2hip_batch_submit", "jp2hip_batch_wait",
-                 "jp2hip_batch_pending", "jp2hip_batch_destroy")
+                 "jp2hip_batch_pending", "jp2hip_batch_destroy", "jp2hip_batch_set_organisation")
 
 
 def _bind():
@@ -77,6 +77,7 @@ def _bind():
     L.jp2hip_batch_pending.argtypes = [c_void_p]
     L.jp2hip_batch_pending.restype = c_int64
     L.jp2hip_batch_destroy.argtypes = [c_void_p]
+    L.jp2hip_batch_set_organisation.argtypes = [c_void_p, POINTER(_lib.Organisation)]
     L._batch_bound = True
     return L
 
@@ -213,7 +214,7 @@ class BatchQueue:
 
     def __init__(self, device: int = 0, contexts: int = 12, reader_threads: int = 4,
                  uploader_threads: int = 4, host_threads: int = 0, delete_after_upload: bool = True,
-                 write_output: bool = True, upload=None):
+                 write_output: bool = True, upload=None, tlm: bool = False):
         # one HW queue per context (+4 for the runtime); only takes effect if
         # nothing in this process has initialised HIP yet
         os.environ.setdefault("GPU_MAX_HW_QUEUES", str(max(4, min(32, (contexts or 12) + 4))))
@@ -233,6 +234,15 @@ class BatchQueue:
                                  None) != 0:
             raise _lib.Jp2hipError(_lib.last_error())
         self._h = h
+        if tlm:  # ORGgen_tlm on every context of the queue (before the first submit)
+            self.set_organisation(tlm=tlm)
+
+    def set_organisation(self, tlm: bool | int = 0, reserved=(0, 0, 0)):
+        """jp2hip_batch_set_organisation: Encoder.set_organisation on every
+        context of the queue; only before the first submit."""
+        org = _lib.Organisation(int(tlm), (c_int32 * 3)(*reserved))
+        if _bind().jp2hip_batch_set_organisation(self._h, byref(org)) != 0:
+            raise _lib.Jp2hipError(_lib.last_error() or "the queue has taken a job already")
 
     def submit(self, job: int, image_id: str, tiff: os.PathLike | str, jpx: os.PathLike | str,
                conversion: int = _lib.LOSSLESS, rcp: _lib.Recipe | None = None):

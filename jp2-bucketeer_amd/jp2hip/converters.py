@@ -104,7 +104,8 @@ class GpuConverter(Converter):
     an image of at least ``split_min_pixels`` (default 256 MP, or
     ``JP2HIP_SPLIT_MIN_PIXELS``) is tile-split across those GPUs inside
     jp2hip_encode_file (jp2hip_split_peers), a smaller one takes a pool
-    context.
+    context.  ``tlm=True`` is Kakadu's ``ORGgen_tlm=yes``: every file gets
+    TLM marker segments (Encoder.set_organisation on every context).
 
     Safe for concurrent callers (the reference runs one ImageWorkerVerticle
     thread, MainVerticle.java:229-231; raising that count gives each call its
@@ -116,7 +117,7 @@ class GpuConverter(Converter):
     SPLIT_MIN_PIXELS = 256_000_000
 
     def __init__(self, devices: list[int] | None = None, host_threads: int = 0, per_gpu: int | None = None,
-                 split_devices: list[int] | None = None, split_min_pixels: int | None = None):
+                 split_devices: list[int] | None = None, split_min_pixels: int | None = None, tlm: bool = False):
         self.tmp_dir = Path(tempfile.gettempdir()) / self.WORKING_DIR_NAME
         self._pool, self._free = [], []
         self._cv = threading.Condition()
@@ -141,6 +142,8 @@ class GpuConverter(Converter):
             self._pool = [_lib.Encoder(d, host_threads) for _ in range(max(1, per_gpu)) for d in devices]
             if len(split_devices) > 1:
                 self._split = _lib.Encoder(split_devices[0], host_threads)
+                if tlm:  # before the peers: they inherit it
+                    self._split.set_organisation(tlm=True)
                 self._split.split_peers(list(split_devices[1:]), split_min_pixels)
                 self.split_world = len(split_devices)
         except _lib.Jp2hipError as e:
@@ -149,6 +152,10 @@ class GpuConverter(Converter):
             raise IOError(BUCKETEER_001.format(f"(GPU converter init: {e})")) from e
         if not self._pool:
             raise IOError(BUCKETEER_001.format("(no gfx950 device)"))
+        self.tlm = bool(tlm)
+        if tlm:  # ORGgen_tlm: TLM marker segments in every file this converter writes
+            for e in self._pool:
+                e.set_organisation(tlm=True)
         self._free = list(self._pool)
         # the slow configurations the library can see (queues, SDMA): logged once
         self.env_advice = _lib.env_check()
@@ -166,6 +173,7 @@ class GpuConverter(Converter):
         c._pool, c._free, c._cv = [], [], threading.Condition()
         c._split, c._split_lock, c.split_world = None, threading.Lock(), 1
         c._closed = False
+        c.tlm = False
         c.unavailable = reason
         return c
 

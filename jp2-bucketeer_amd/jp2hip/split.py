@@ -215,7 +215,11 @@ def _band_units(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
 
 def encode_split(encoder, d_ptr: int, nbytes: int, layout: Layout, conversion: int,
                  group: _Group | None = None, rcp=None):
-    """This rank's part: (bytes, file_offset, file_len, Stats).  Collective."""
+    """This rank's part: (bytes, file_offset, file_len, Stats).  Collective --
+    in the recipe and in the organisation: every rank's encoder has had the
+    same ``set_organisation`` (with ``tlm`` the ranks sum their tile-part
+    lengths through ``group`` and rank 0 writes the TLM marker segments;
+    ``file_len`` and the later ranks' offsets count them)."""
     sp = (group or SingleGroup()).split()
     return encoder.encode_device_split(d_ptr, nbytes, layout, conversion, sp, rcp)
 
