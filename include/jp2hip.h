@@ -289,6 +289,52 @@ int jp2hip_set_memory_limits(jp2hip_ctx *ctx, int64_t soft, int64_t hard);
  * reserved non-zero). */
 int jp2hip_set_organisation(jp2hip_ctx *ctx, const jp2hip_organisation *org);
 
+/* Tile-part divisions besides the recipe's (Kakadu's ORGtparts takes any
+ * subset of R|L|C; R stays recipe.tparts_r). */
+#define JP2HIP_TPARTS_L 2 /* a new tile-part where the layer changes     */
+#define JP2HIP_TPARTS_C 4 /* a new tile-part where the component changes */
+
+/* The tile-part divisions of every later encode on ctx, its tile-split peers
+ * included (peers added later inherit them): letters = 0, JP2HIP_TPARTS_L,
+ * JP2HIP_TPARTS_C or both; 0 restores the output without them.  A tile sends
+ * its packets in the recipe's progression order (jp2hip_packet_sequence), and
+ * a new tile-part starts before every packet that differs from the one before
+ * it in a flagged index: resolution (R, when recipe.tparts_r is set -- still
+ * RLCP and RPCL only), layer (L), component (C).  Each tile-part has its own
+ * SOT (TPsot 0, 1, ...; TNsot = the tile's count on its last tile-part, else
+ * 0), PLT (when recipe.plt is set) and SOD; no packet byte or Nsop changes.
+ * In the file, per -flush_period stripe, part 0 of every tile of the stripe
+ * comes first, then part 1, ...: with LRCP and L a stripe holds layer 0 of
+ * all its tiles, then layer 1.  Letters that cut nowhere (L with one layer)
+ * give the file without them, byte for byte.  An encode whose divisions give
+ * a tile more than 255 tile-parts (TNsot is 8 bits) is refused with a message
+ * that names the tile, the count and the letters.
+ * A rate-driven encode with letters is the encode without them whose byte
+ * target is E lower (floored at 0, on top of the TLM's T), E = (14 + 5 * plt)
+ * * (tile-parts with the letters - tile-parts without): the headers of the
+ * added tile-parts are part of the code-stream the target bounds.  That
+ * equivalence is exact where every PLT, divided or not, is one marker
+ * segment, which holds when no undivided tile-part has more than 13 106
+ * packets (5 bytes * 13 106 <= 65 532); beyond that the file is still a valid
+ * code-stream, but its rate-driven packets are not claimed to be those of the
+ * encode at the lower target.  Lossless encodes select as without letters.
+ * Kdu-Layer-Info's L(bytes) and stats.out_bytes count the real headers.
+ * Collective over a caller's callback, like the recipe: every rank sets the
+ * same letters.  Not to be called while ctx is encoding.  Returns 0, or < 0
+ * with a message: for bit 1 (R) one that points at recipe.tparts_r, for any
+ * other bit one that names it. */
+int jp2hip_set_tile_part_divisions(jp2hip_ctx *ctx, int32_t letters);
+
+/* Host-only, exported for tests (like jp2hip_packet_sequence): the tile-parts
+ * of tile `tile` of a width x height image under `recipe` and `letters` --
+ * returns their count and writes the place in the tile's packet sequence at
+ * which each starts (first[0] = 0; the first min(count, cap) of them).
+ * Returns < 0 with a message for anything the encodes refuse (the recipe, the
+ * letters, more than 255 tile-parts in a tile, a tile outside the image). */
+int64_t jp2hip_tile_parts(int32_t width, int32_t height, int32_t components, int32_t bits,
+                          const jp2hip_recipe *recipe, int32_t letters, int32_t tile, uint32_t *first,
+                          int64_t cap);
+
 /* Host-only, exported for tests (like jp2hip_packet_sequence): the TLM marker
  * segments for n tile-parts in file order -- per segment FF55, Ltlm = 4 + 6 k,
  * Ztlm 0, 1, ..., Stlm 0x60, then k <= 10921 pairs (tiles[i], lengths[i]),
@@ -526,6 +572,9 @@ int jp2hip_batch_create(jp2hip_batch **out, const jp2hip_batch_config *cfg, jp2h
 /* jp2hip_set_organisation on every context of the queue; before the first
  * submit (< 0 after it, or for a refused organisation). */
 int jp2hip_batch_set_organisation(jp2hip_batch *b, const jp2hip_organisation *org);
+/* jp2hip_set_tile_part_divisions on every context of the queue; before the
+ * first submit (< 0 after it, or for refused letters). */
+int jp2hip_batch_set_tile_part_divisions(jp2hip_batch *b, int32_t letters);
 /* Queue one image: convert `tiff_path` into `jpx_path` (written atomically)
  * with `conversion` (recipe NULL -> Bucketeer recipe), then upload it under
  * `image_id`.  Never blocks on the GPU; returns < 0 after close. */

@@ -262,6 +262,51 @@ int jp2hip_set_organisation(jp2hip_ctx *ctx, const jp2hip_organisation *org) {
     return 0;
 }
 
+// the letters a context may hold; the message for the ones it may not
+static bool letters_ok(int32_t letters, std::string &err) {
+    if (letters & 1) {
+        err = "tile-part divisions: R (bit 1) is the recipe's: set recipe.tparts_r";
+        return false;
+    }
+    if (letters & ~(JP2HIP_TPARTS_L | JP2HIP_TPARTS_C)) {
+        err = "tile-part divisions: " + std::to_string(letters) + " has a bit that is neither JP2HIP_TPARTS_L (2) nor " +
+              "JP2HIP_TPARTS_C (4)";
+        return false;
+    }
+    return true;
+}
+
+int jp2hip_set_tile_part_divisions(jp2hip_ctx *ctx, int32_t letters) {
+    std::string err;
+    if (!letters_ok(letters, err)) return fail(err);
+    if (!ctx) return fail("null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->tparts = letters;
+    for (jp2hip_ctx *p : ctx->peers)
+        if (jp2hip_set_tile_part_divisions(p, letters) != 0) return -1;
+    return 0;
+}
+
+int64_t jp2hip_tile_parts(int32_t width, int32_t height, int32_t components, int32_t bits,
+                          const jp2hip_recipe *recipe, int32_t letters, int32_t tile, uint32_t *first, int64_t cap) {
+    if (!recipe || cap < 0 || (cap > 0 && !first)) return fail("null recipe, or no room for the tile-parts");
+    // the plan an encode of this image builds and the checks it makes, then
+    // the function its tier-2 tables take the tile-parts from
+    jp2hip::Plan plan;
+    std::string err;
+    jp2hip_recipe rc = *recipe;
+    if (!letters_ok(letters, err) || !jp2hip::resolve_tiles(rc, width, height, err) ||
+        !jp2hip::build_plan(plan, rc, width, height, components, bits, err))
+        return fail(err);
+    std::vector<int> count;
+    if (!jp2hip::tile_part_counts(plan, letters, count, err)) return fail(err);
+    if (tile < 0 || tile >= plan.ntx * plan.nty) return fail("tile index outside the image's tiles");
+    std::vector<uint32_t> f;
+    const int n = jp2hip::tile_part_runs(plan, tile, letters, nullptr, f);
+    std::copy(f.begin(), f.begin() + (ptrdiff_t)std::min<int64_t>(cap, (int64_t)f.size()), first);
+    return n;
+}
+
 int64_t jp2hip_tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n, uint8_t *dst, size_t cap) {
     if (!tiles || !lengths || n < 0) return fail("null tiles or lengths, or a negative count");
     if (n > jp2hip::kTlmMaxEntries)
@@ -451,6 +496,7 @@ int jp2hip_split_peers(jp2hip_ctx *ctx, const int32_t *ordinals, int32_t n, int6
             return fail(e);
         }
         p->org = ctx->org;  // (jp2hip_set_organisation: peers added later inherit it)
+        p->tparts = ctx->tparts;  // (jp2hip_set_tile_part_divisions likewise)
         made.push_back(p);
     }
     for (jp2hip_ctx *p : ctx->peers) jp2hip_destroy(p);

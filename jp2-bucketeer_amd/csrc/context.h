@@ -20,7 +20,12 @@ struct PlanCache {
     jp2hip_recipe rc;
     int w = 0, h = 0, nc = 0, bits = 0;
     jp2hip::Plan plan;
+    // the tables are the plan's cut by the context's tile-part divisions
+    // (tabs.letters; tabs_ok false: none built for this plan yet), which are
+    // no part of the key above: a change of letters rebuilds the tables alone
     jp2hip::T2Tables tabs;
+    bool tabs_ok = false;
+    int64_t division_bytes = 0;  // tile_part_division_bytes of (plan, tabs.letters)
     std::vector<uint8_t> mh0;
 };
 
@@ -38,6 +43,9 @@ struct jp2hip_ctx {
     // cache's key (the plan, its tables and the main header up to the TLM
     // are the same with and without it)
     jp2hip_organisation org{};
+    // jp2hip_set_tile_part_divisions: JP2HIP_TPARTS_L | _C, read by every
+    // encode; the tier-2 tables depend on it, the plan does not
+    int32_t tparts = 0;
     // tile-split members (jp2hip_split_peers): images of at least
     // split_min_pixels are encoded by this context (rank 0) and these
     // (ranks 1..), owned here

@@ -63,16 +63,17 @@ namespace {
 // A rate-driven encode's target (bytes): the floor(rate * W * H / 8) the
 // oracle's predict_and_code uses; slope prediction's is the same, -1 = off
 // (an image so small that the target is 0 bytes still predicts, as the
-// oracle does: 0 is a target like any other).  tlm: the bytes of the TLM marker
-// segments, part of the code-stream the target bounds -- a rate-driven encode
-// with a TLM is the encode without one whose target is that much lower
-// (floored at 0), so everything the target steers sees the lower one.
-int64_t rate_target_of(const jp2hip_recipe &rc, int w, int h, int64_t tlm) {
+// oracle does: 0 is a target like any other).  org: the bytes of the TLM marker
+// segments plus those the L / C tile-part divisions add
+// (tile_part_division_bytes), parts of the code-stream the target bounds -- a
+// rate-driven encode with either is the encode without whose target is that
+// much lower (floored at 0), so everything the target steers sees the lower one.
+int64_t rate_target_of(const jp2hip_recipe &rc, int w, int h, int64_t org) {
     const int64_t target = (int64_t)std::floor(rc.rate_bpp * (double)w * (double)h / 8.0);
-    return tlm ? std::max<int64_t>(0, target - tlm) : target;
+    return org ? std::max<int64_t>(0, target - org) : target;
 }
-int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h, int64_t tlm) {
-    return rc.slope_skip && rc.rate_bpp > 0.0 ? rate_target_of(rc, w, h, tlm) : -1;
+int64_t skip_target_of(const jp2hip_recipe &rc, int w, int h, int64_t org) {
+    return rc.slope_skip && rc.rate_bpp > 0.0 ? rate_target_of(rc, w, h, org) : -1;
 }
 // The rate loop's first budget: its header estimate (16 bytes per packet)
 // lands the usual encode under the target (C2: 8 985 521 of 9 000 000 bytes).
@@ -210,8 +211,8 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     if (!pc.valid || pc.w != lay->width || pc.h != lay->height || pc.nc != lay->components || pc.bits != lay->bits ||
         std::memcmp(&pc.rc, &rc, sizeof rc) != 0) {
         pc.valid = false;
+        pc.tabs_ok = false;
         if (!build_plan(pc.plan, rc, lay->width, lay->height, lay->components, lay->bits, err)) return fail(err);
-        t2_tables(pc.plan, 0, pc.plan.ntx * pc.plan.nty, 0, pc.tabs);
         main_header(pc.plan, pc.mh0, nullptr, nullptr);
         pc.rc = rc;
         pc.w = lay->width; pc.h = lay->height; pc.nc = lay->components; pc.bits = lay->bits;
@@ -220,13 +221,25 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         ctx->reused |= JP2HIP_REUSED_PLAN;
     }
     const Plan &plan = pc.plan;
+    // the tile-part divisions are no part of the plan's key: other letters on
+    // the same plan cut its tables anew
+    if (!pc.tabs_ok || pc.tabs.letters != ctx->tparts) {
+        pc.tabs_ok = false;
+        t2_tables(plan, 0, plan.ntx * plan.nty, 0, pc.tabs, ctx->tparts);
+        if (!tile_parts_fit(plan, pc.tabs, err)) return fail(err);
+        // E (rate-driven encodes only; a lossless one never sees it)
+        pc.division_bytes =
+            rc.rate_bpp > 0.0 ? tile_part_division_bytes(plan, ctx->tparts, (int64_t)pc.tabs.tp.size()) : 0;
+        pc.tabs_ok = true;
+    }
     const bool prof = ctx->cfg.profile != 0;
     StageTimes st;
     // the organisation is no part of the cached plan: its bytes come from the tile-part count alone
     const int64_t tlm = ctx->org.tlm ? tlm_bytes((int64_t)pc.tabs.tp.size()) : 0;
     if (ctx->org.tlm && (int64_t)pc.tabs.tp.size() > kTlmMaxEntries)
         return fail("tlm: more tile-parts than 256 TLM marker segments hold");
-    int64_t skip_target = skip_target_of(rc, plan.w, plan.h, tlm);
+    const int64_t E = pc.division_bytes;  // what the L / C divisions add
+    int64_t skip_target = skip_target_of(rc, plan.w, plan.h, tlm + E);
     // tier-2 tables first: every host->device copy of the encode is issued
     // while the stream is idle (a copy queued behind kernels holds up the
     // copy engine for the other contexts)
@@ -262,9 +275,11 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         // heavier takes a second wait for its next iterations
         RateState init;
         std::memset(&init, 0, sizeof init);
-        init.target = rate_target_of(rc, plan.w, plan.h, tlm);
+        init.target = rate_target_of(rc, plan.w, plan.h, tlm + E);
         init.budget = first_budget_of(plan, init.target);
-        init.fixed = (int64_t)mh_bytes + 2;
+        // the cs_bytes the loop compares leaves E out, as it leaves the TLM
+        // out: the encode without letters, at the lower target
+        init.fixed = (int64_t)mh_bytes + 2 - E;
         init.skip_target = skip_target;
         RateState rs;
         bool restart = true;
@@ -292,7 +307,7 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
             if (rs.halt) break;
         }
         iters = rs.iters;
-        cs_bytes = rs.cs_bytes + tlm;  // (= init.fixed + sum.part_bytes: device_common.h rate_step)
+        cs_bytes = rs.cs_bytes + tlm + E;  // (rs.cs_bytes = init.fixed + sum.part_bytes: device_common.h rate_step)
     }
     FilePart fp{plan, plan, true, true, true};
     fp.size(meta, mh_bytes, sum.part_bytes, (size_t)tlm);
@@ -369,13 +384,26 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // TLM (collective, like the recipe: every rank's context has the same
     // organisation): its bytes are known from the full plan alone (so a plan
     // with too many tile-parts fails every rank here, before any exchange)
-    const int64_t ntp_full = ctx->org.tlm ? tile_parts_in(full, 0, full.ntx * full.nty) : 0;
+    // The tile-part divisions are collective in the same way; a tile they cut
+    // into too many parts fails every rank here as well.  ntp[t]: tile-parts
+    // of the full plan's tiles before t (file order keeps a band's contiguous)
+    const int letters = ctx->tparts;
+    const int ntiles = full.ntx * full.nty;
+    std::vector<int64_t> ntp((size_t)ntiles + 1, 0);
+    if (ctx->org.tlm || letters) {
+        std::vector<int> count;
+        if (!tile_part_counts(full, letters, count, err)) return fail(err);
+        for (int t = 0; t < ntiles; t++) ntp[(size_t)t + 1] = ntp[(size_t)t] + count[(size_t)t];
+    }
+    const int64_t ntp_full = ctx->org.tlm ? ntp[(size_t)ntiles] : 0;
     if (ntp_full > kTlmMaxEntries) return fail("tlm: more tile-parts than 256 TLM marker segments hold");
     const int64_t tlm = tlm_bytes(ntp_full);
+    // E: what the L / C divisions add (rate-driven encodes only)
+    const int64_t E = rc.rate_bpp > 0.0 ? tile_part_division_bytes(full, letters, ntp[(size_t)ntiles]) : 0;
     // slope prediction over the whole image: the plane histogram is summed
     // over ranks (one all-reduce of kSlopeBins + 1 int64, the last a failure
     // flag, so a rank that failed earlier still joins the exchange)
-    int64_t skip_target = skip_target_of(rc, full.w, full.h, tlm);
+    int64_t skip_target = skip_target_of(rc, full.w, full.h, tlm + E);
     bool hist_done = false;
     GpuEncoder::HistReduce reduce = [&](std::vector<int64_t> &h) {
         hist_done = true;
@@ -389,7 +417,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     T2Tables tabs;  // loaded before the front (host->device copies on an idle stream)
     const int tile0 = sub.tile0, tile1 = sub.tile0 + full.ntx * (tr1 - tr0);
     if (ok && have) {
-        t2_tables(full, tile0, tile1, sub.block0, tabs);
+        t2_tables(full, tile0, tile1, sub.block0, tabs, letters);
         ok = ctx->gpu.t2_load(sub, tabs, err);
     }
     ok = ok && (!have || ctx->gpu.run_front(d_src, *lay, sub, prof, st, err, skip_target, &reduce, true));
@@ -436,7 +464,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
             }
         }
         if (!exchange(v, 1, rok) || !rok) return false;
-        cs_bytes = (int64_t)mh.size() + 2 + v[0];
+        cs_bytes = (int64_t)mh.size() + 2 + v[0] - E;  // (without E, as the target: added back below)
         g_tp_hdr = v[2];
         g_layer.assign(v.begin() + 3, v.begin() + 3 + L);
         iters++;
@@ -465,7 +493,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         ok = ok && (!have || ctx->gpu.segments(sub, keys, cum, err));
         std::vector<int64_t> flag(1);
         if (!exchange(flag, 0, ok) || !ok) return fail(err);
-        const int64_t target = rate_target_of(rc, full.w, full.h, tlm);  // (cs_bytes: without the TLM, as the target)
+        const int64_t target = rate_target_of(rc, full.w, full.h, tlm + E);  // (cs_bytes: without the TLM and E, as the target)
         int64_t budget = first_budget_of(full, target);
         bool rerun = false;
         for (int it = 0; it < 8; it++) {
@@ -500,7 +528,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     std::vector<uint32_t> tp_len;
     if (ready && have && tlm) {
         ready = ctx->gpu.t2_tp_lengths(tp_len, err);
-        if (ready && (int64_t)tp_len.size() != tile_parts_in(full, tile0, tile1)) {
+        if (ready && (int64_t)tp_len.size() != ntp[(size_t)tile1] - ntp[(size_t)tile0]) {
             ready = false;
             err = "tlm: the band's tile-part count differs from its plan's";
         }
@@ -526,7 +554,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     if (tlm) {
         constexpr int64_t kTlmChunk = 1024;
         std::vector<int64_t> all((size_t)ntp_full, 0);
-        const int64_t first = tile_parts_in(full, 0, tile0);
+        const int64_t first = tp_len.empty() ? 0 : ntp[(size_t)tile0];
         for (size_t i = 0; i < tp_len.size(); i++) all[(size_t)first + i] = (int64_t)tp_len[i];
         for (int64_t c0 = 0; c0 < ntp_full; c0 += kTlmChunk)
             if (!allreduce(all.data() + c0, (int)std::min(kTlmChunk, ntp_full - c0))) {
@@ -535,14 +563,14 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
             }
         if (rank == 0) {
             std::vector<uint16_t> tiles;
-            tile_part_order(full, 0, full.ntx * full.nty, tiles);
+            tile_part_order(full, 0, ntiles, tiles, letters);
             std::vector<uint32_t> lens(all.begin(), all.end());
             tlm_seg.resize((size_t)tlm);
             tlm_segments(tiles.data(), lens.data(), ntp_full, tlm_seg.data());
             fp.tlm_host = tlm_seg.data();
         }
     }
-    cs_bytes += tlm;
+    cs_bytes += tlm + E;
     if (finish_part(ctx, fp, meta, K, g_tp_hdr, g_layer.data(), cs_bytes, sum, buf, st, out, out_len, stats, t_start,
                     0.0, (int64_t)flen, iters))
         return -1;

@@ -273,6 +273,7 @@ class GpuEncoder {
     bool t2_wave = true;  // precincts of <= 64 blocks: k_t2_wave (layer assignment fused in)
     bool t2_seq = false;  // a progression order other than RPCL: t2seq holds its forward map
     uint64_t front_gen = 0, t2_gen = 0;  // plan generation whose tables are resident
+    int t2_letters = 0;                  // ... and the tile-part divisions of the tier-2 tables
     int reuse = 0;                   // reuse_bits() of the current encode
     bool reuse_front_noted = false;  // (its first run_front is the one noted: a repeat finds its own uploads)
     T2Summary *h_sum = nullptr;

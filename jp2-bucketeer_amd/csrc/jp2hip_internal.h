@@ -180,24 +180,37 @@ struct PrecDesc {
     uint16_t nsop_step;
 };
 static_assert(sizeof(PrecDesc) == 36, "PrecDesc layout");
+// A tile-part: a run of its tile's packet sequence (tile_part_runs).
 struct TpDesc {
     int32_t tile, tpsot, tnsot;  // SOT fields (Isot, TPsot, TNsot)
-    int32_t prec0, nprec;        // its precincts in the PrecDesc table
+    // the precincts (PrecDesc table) its packets come from, first to last in
+    // storage order -- host side only; without the L and C divisions the
+    // tile-parts' ranges are disjoint and hold exactly their packets
+    int32_t prec0, nprec;
+    // what the kernels walk: its packets are the places [s0, s0 + ns) of the
+    // forward map T2Tables::seq (no map, RPCL: the packets stored there)
+    uint32_t s0, ns;
 };
+static_assert(sizeof(TpDesc) == 28, "TpDesc layout");
 struct T2Tables {
     std::vector<PrecDesc> prec;
     std::vector<TpDesc> tp;   // code-stream order
-    // Forward map of the progression order: a tile-part stores its packets at
-    // [prec0 * L, (prec0 + nprec) * L), and the s-th packet it sends is packet
-    // seq[prec0 * L + s].  Empty = identity (RPCL: storage order is sequence
-    // order).
+    // Forward map of the progression order: the packets of the tables' i-th
+    // tile lie at [b, b + n) in storage and in this map alike (n its packet
+    // count), and the s-th packet the tile sends is packet seq[b + s]; a
+    // tile-part takes a run of those places.  Empty = identity (RPCL: storage
+    // order is sequence order).
     std::vector<uint32_t> seq;
     int64_t tt_nodes = 0;
     int max_prec_blocks = 0;  // code-blocks of the largest precinct
+    int letters = 0;          // the L / C divisions the tile-parts were cut with
 };
 // Tables for tiles [tile0, tile1) of `P` (blocks rebased by -block0: a
 // tile-split rank's blocks are its sub-plan's).
-void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T);
+// `letters`: JP2HIP_TPARTS_L | _C (jp2hip_set_tile_part_divisions); the
+// caller checks the tile-part counts (tile_parts_fit, tile_part_counts)
+// before the tables reach the device: TNsot is stored as it comes.
+void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T, int letters = 0);
 // Tile t's packets in the order rc.progression sends them (B.12.1; no
 // component is subsampled): each entry the packet's storage index within the
 // tile, p * L + l for the tile's p-th precinct in (resolution, py, px,
@@ -216,14 +229,37 @@ int64_t tlm_bytes(int64_t ntp);
 // jp2hip_tlm_segments; the single-GPU encode writes the same bytes on the
 // device (t2_device.hip k_t2_tlm).
 void tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n, uint8_t *dst);
-// Tile-parts of tile t (one per non-empty resolution with tparts_r, else one),
-// of tiles [tile0, tile1), and the tile of each of their tile-parts in file
-// order -- T2Tables::tp's order and count without the precinct tables.
+// Tile t's tile-parts as runs of its packet sequence (ORGtparts): the
+// divisions are R (rc.tparts_r) plus `letters` (JP2HIP_TPARTS_L | _C), and a
+// tile-part starts at place 0 and before every place whose packet differs
+// from the one before it in a flagged index -- resolution for R, layer for L,
+// component for C.  `first` receives the places the parts start at; returns
+// their count.  seq: the tile's packet_sequence when the caller has it (else
+// it is built here; RPCL needs none).  The only place that knows the rule:
+// t2_tables, the counts below and jp2hip_tile_parts all come here.
+int tile_part_runs(const Plan &P, int t, int letters, const std::vector<uint32_t> *seq, std::vector<uint32_t> &first);
+// TNsot is 8 bits: false, with a message that names the tile, its count and
+// the letters, when a tile's divisions give more than 255 tile-parts -- from
+// the counts of every tile of P (count[t]; a split's ranks, jp2hip_tile_parts),
+// or from tables already built for all of them (the single encode).
+constexpr int kMaxTileParts = 255;
+bool tile_part_counts(const Plan &P, int letters, std::vector<int> &count, std::string &err);
+bool tile_parts_fit(const Plan &P, const T2Tables &T, std::string &err);
+// Tile-parts of tile t, of tiles [tile0, tile1), and the tile of each of
+// their tile-parts in file order -- T2Tables::tp's order and count without
+// the precinct tables: per -flush_period stripe, part 0 of every tile of the
+// stripe, then part 1, ... (a tile with fewer parts drops out).
 // (Plan::ntileparts is the rate loop's header estimate: it counts a tile-part
-// per resolution whatever tparts_r says.)
-int tile_part_count(const Plan &P, int t);
-int64_t tile_parts_in(const Plan &P, int tile0, int tile1);
-void tile_part_order(const Plan &P, int tile0, int tile1, std::vector<uint16_t> &tiles);
+// per resolution whatever the divisions are.)
+int tile_part_count(const Plan &P, int t, int letters = 0);
+int64_t tile_parts_in(const Plan &P, int tile0, int tile1, int letters = 0);
+void tile_part_order(const Plan &P, int tile0, int tile1, std::vector<uint16_t> &tiles, int letters = 0);
+// The bytes the L / C divisions add to a code-stream whose PLTs are one
+// segment each: SOT + SOD (14) and a PLT header (5, with plt) per tile-part
+// they add; ntp: the image's tile-parts with the letters.  A rate-driven
+// encode with letters is the encode without them whose target is this much
+// lower (jp2hip.h).
+int64_t tile_part_division_bytes(const Plan &P, int letters, int64_t ntp);
 // What the host reads back after a tier-2 sizing pass (one D2H per pass).
 struct T2Summary {
     int64_t part_bytes;               // tile-parts of the tiles coded (SOT .. last packet)

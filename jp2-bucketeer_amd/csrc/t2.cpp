@@ -10,7 +10,10 @@
 // The layout is the one oracle/jp2_oracle.c writes (write_codestream).
 // The other progression orders (LRCP, RLCP, PCRL, CPRL) keep the packets and
 // their storage; packet_sequence says in which order a tile sends them, and
-// t2_tables turns that into the device's forward map and SOP numbers.
+// t2_tables turns that into the device's forward map and SOP numbers.  A
+// tile-part is a run of that sequence: tile_part_runs cuts it where the
+// resolution (R), the layer (L) or the component (C) changes, whichever of
+// ORGtparts' letters are set (jp2hip_set_tile_part_divisions for L and C).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -189,28 +192,108 @@ void packet_sequence(const Plan &P, int t, std::vector<uint32_t> &seq) {
         for (int l = 0; l < L; l++) seq.push_back(e.p * (uint32_t)L + (uint32_t)l);
 }
 
-void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
+int tile_part_runs(const Plan &P, int t, int letters, const std::vector<uint32_t> *seq, std::vector<uint32_t> &first) {
+    const jp2hip_recipe &rc = P.rc;
+    const int L = rc.layers;
+    const bool byR = rc.tparts_r != 0, byL = (letters & JP2HIP_TPARTS_L) != 0, byC = (letters & JP2HIP_TPARTS_C) != 0;
+    first.assign(1, 0u);
+    if (!byR && !byL && !byC) return 1;
+    // resolution and component of the tile's precincts, in storage order
+    const Tile &Tl = P.tiles[(size_t)t];
+    std::vector<uint16_t> rc_of;  // r << 8 | c
+    for (int r = 0; r <= rc.levels; r++) {
+        const Resolution &R0 = Tl.tc[0].res[r];
+        for (int i = 0; i < R0.npx * R0.npy; i++)
+            for (int c = 0; c < P.nc; c++) rc_of.push_back((uint16_t)((r << 8) | c));
+    }
+    std::vector<uint32_t> own;
+    if (!seq && rc.progression != JP2HIP_ORDER_RPCL) {
+        packet_sequence(P, t, own);
+        seq = &own;
+    }
+    const size_t n = rc_of.size() * (size_t)L;
+    const uint16_t keep = (uint16_t)((byR ? 0xFF00 : 0) | (byC ? 0x00FF : 0));
+    uint32_t prev = 0;
+    for (size_t s = 0; s < n; s++) {
+        const size_t k = seq ? (*seq)[s] : s;
+        // the flagged indices of packet k as one word
+        const uint32_t flagged = (uint32_t)(rc_of[k / (size_t)L] & keep) | (byL ? (uint32_t)(k % (size_t)L) << 16 : 0u);
+        if (s && flagged != prev) first.push_back((uint32_t)s);
+        prev = flagged;
+    }
+    return (int)first.size();
+}
+
+static std::string division_letters(const Plan &P, int letters) {
+    std::string s;
+    if (P.rc.tparts_r) s += 'R';
+    if (letters & JP2HIP_TPARTS_L) s += 'L';
+    if (letters & JP2HIP_TPARTS_C) s += 'C';
+    return s;
+}
+
+static bool too_many(const Plan &P, int t, int n, int letters, std::string &err) {
+    if (n <= kMaxTileParts) return false;
+    err = "tile " + std::to_string(t) + ": " + std::to_string(n) + " tile-parts with ORGtparts=" +
+          division_letters(P, letters) + " (TNsot holds at most " + std::to_string(kMaxTileParts) + ")";
+    return true;
+}
+
+bool tile_part_counts(const Plan &P, int letters, std::vector<int> &count, std::string &err) {
+    count.assign((size_t)(P.ntx * P.nty), 0);
+    for (int t = 0; t < P.ntx * P.nty; t++) {
+        count[(size_t)t] = tile_part_count(P, t, letters);
+        if (too_many(P, t, count[(size_t)t], letters, err)) return false;
+    }
+    return true;
+}
+
+bool tile_parts_fit(const Plan &P, const T2Tables &T, std::string &err) {
+    // a tile's count stands on its last part; the first such tile in tile order is named
+    const TpDesc *worst = nullptr;
+    for (const TpDesc &tp : T.tp)
+        if (tp.tnsot > kMaxTileParts && (!worst || tp.tile < worst->tile)) worst = &tp;
+    return !worst || !too_many(P, worst->tile, worst->tnsot, T.letters, err);
+}
+
+// File order of the tile-parts of tiles [tile0, tile1), whose counts are
+// count[t - tile0]: per -flush_period stripe, part 0 of every tile of the
+// stripe in tile order, then part 1, ... (test.jpx); emit(t, k) for each.
+template <typename F>
+static void file_order(const Plan &P, int tile0, int tile1, const std::vector<int> &count, F emit) {
+    const std::vector<int> ends = flush_stripe_ends(P.nty, P.rc.tile_h, P.h, P.rc.flush_period);
+    int ty0 = 0;
+    for (int e : ends) {
+        const int a = std::max(tile0, ty0 * P.ntx), b = std::min(tile1, e * P.ntx);
+        int most = 0;
+        for (int t = a; t < b; t++) most = std::max(most, count[(size_t)(t - tile0)]);
+        for (int k = 0; k < most; k++)
+            for (int t = a; t < b; t++)
+                if (k < count[(size_t)(t - tile0)]) emit(t, k);
+        ty0 = e;
+    }
+}
+
+void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T, int letters) {
     const jp2hip_recipe &rc = P.rc;
     const int Lv = rc.levels, L = rc.layers;
     const bool resequence = rc.progression != JP2HIP_ORDER_RPCL;
-    std::vector<uint32_t> tseq, pos;
+    std::vector<uint32_t> tseq, pos, first;
     T.prec.clear();
     T.tp.clear();
     T.seq.clear();
     T.tt_nodes = 0;
     T.max_prec_blocks = 0;
+    T.letters = letters;
     // tile-parts per tile, in tile order first
     std::vector<std::vector<TpDesc>> per_tile((size_t)std::max(0, tile1 - tile0));
+    std::vector<int> count(per_tile.size(), 0);
     for (int t = tile0; t < tile1; t++) {
         const Tile &Tl = P.tiles[t];
         int nsop = 0;
         const size_t tile_prec0 = T.prec.size();
-        std::vector<TpDesc> &tps = per_tile[(size_t)(t - tile0)];
         for (int r = 0; r <= Lv; r++) {
             const Resolution &R0 = Tl.tc[0].res[r];
-            if (R0.npx * R0.npy == 0) continue;
-            if (rc.tparts_r || tps.empty()) tps.push_back(TpDesc{t, (int32_t)tps.size(), 0, (int32_t)T.prec.size(), 0});
-            TpDesc &tp = tps.back();
             for (int py = 0; py < R0.npy; py++)
                 for (int px = 0; px < R0.npx; px++)
                     for (int c = 0; c < P.nc; c++) {
@@ -232,17 +315,16 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
                         }
                         T.max_prec_blocks = std::max(T.max_prec_blocks, blocks);
                         T.prec.push_back(d);
-                        tp.nprec++;
                         nsop += L;
                     }
         }
-        for (TpDesc &tp : tps) tp.tnsot = (&tp == &tps.back()) ? (int32_t)tps.size() : 0;
+        const uint32_t base = (uint32_t)(tile_prec0 * (size_t)L);
+        const uint32_t npk = (uint32_t)((T.prec.size() - tile_prec0) * (size_t)L);
         if (resequence) {
-            // another order: the tile's sequence (its tile-parts take runs of
-            // it: one part, or RLCP's part per resolution), and each packet's
-            // place in it as its Nsop -- nsop0 for layer 0, then nsop_step a
-            // layer: 1 where layers are innermost, else the packets of one
-            // layer of the resolution (RLCP) or of the tile (LRCP)
+            // another order: the tile's sequence, and each packet's place in
+            // it as its Nsop -- nsop0 for layer 0, then nsop_step a layer: 1
+            // where layers are innermost, else the packets of one layer of
+            // the resolution (RLCP) or of the tile (LRCP)
             packet_sequence(P, t, tseq);
             pos.resize(tseq.size());
             for (size_t s = 0; s < tseq.size(); s++) pos[tseq[s]] = (uint32_t)s;
@@ -251,55 +333,63 @@ void t2_tables(const Plan &P, int tile0, int tile1, int block0, T2Tables &T) {
                 T.prec[i].nsop0 = (int32_t)pos[k];
                 T.prec[i].nsop_step = L > 1 ? (uint16_t)(pos[k + 1] - pos[k]) : 1;
             }
-            const uint32_t base = (uint32_t)(tile_prec0 * (size_t)L);
             for (uint32_t s : tseq) T.seq.push_back(base + s);
         }
-    }
-    // code-stream order: per -flush_period stripe, resolution 0 of every tile,
-    // then resolution 1, ... (test.jpx; t2_emit_part does the same on the host)
-    const std::vector<int> ends = flush_stripe_ends(P.nty, rc.tile_h, P.h, rc.flush_period);
-    int ty0 = 0;
-    for (int e : ends) {
-        const int a = std::max(tile0, ty0 * P.ntx), b = std::min(tile1, e * P.ntx);
-        for (int k = 0; k <= Lv; k++)
-            for (int t = a; t < b; t++) {
-                const std::vector<TpDesc> &tps = per_tile[(size_t)(t - tile0)];
-                if (k < (int)tps.size()) T.tp.push_back(tps[(size_t)k]);
+        // its tile-parts: the runs its divisions cut the sequence into
+        if (!npk) continue;
+        const int ntp = tile_part_runs(P, t, letters, resequence ? &tseq : nullptr, first);
+        std::vector<TpDesc> &tps = per_tile[(size_t)(t - tile0)];
+        for (int i = 0; i < ntp; i++) {
+            const uint32_t s0 = first[(size_t)i], s1 = i + 1 < ntp ? first[(size_t)i + 1] : npk;
+            uint32_t lo = UINT32_MAX, hi = 0;  // the precincts the run's packets come from
+            for (uint32_t s = s0; s < s1; s++) {
+                const uint32_t p = (resequence ? tseq[s] : s) / (uint32_t)L;
+                lo = std::min(lo, p);
+                hi = std::max(hi, p);
             }
-        ty0 = e;
+            TpDesc tp;
+            tp.tile = t;
+            tp.tpsot = i;
+            tp.tnsot = i == ntp - 1 ? ntp : 0;
+            tp.prec0 = (int32_t)(tile_prec0 + lo);
+            tp.nprec = (int32_t)(hi - lo + 1);
+            tp.s0 = base + s0;
+            tp.ns = s1 - s0;
+            tps.push_back(tp);
+        }
+        count[(size_t)(t - tile0)] = ntp;
     }
+    file_order(P, tile0, tile1, count, [&](int t, int k) { T.tp.push_back(per_tile[(size_t)(t - tile0)][(size_t)k]); });
 }
 
-// ---- TLM marker segments (A.7.1; jp2hip_set_organisation) ----
+// ---- tile-part counts and order without the tables; TLM marker segments
+// (A.7.1; jp2hip_set_organisation) ----
 
-int tile_part_count(const Plan &P, int t) {
-    int n = 0;
-    for (int r = 0; r <= P.rc.levels; r++) {
-        const Resolution &R0 = P.tiles[(size_t)t].tc[0].res[r];
-        if (R0.npx * R0.npy) n++;
-    }
-    return P.rc.tparts_r ? n : std::min(n, 1);
+int tile_part_count(const Plan &P, int t, int letters) {
+    const Tile &Tl = P.tiles[(size_t)t];
+    bool any = false;
+    for (int r = 0; r <= P.rc.levels && !any; r++) any = Tl.tc[0].res[r].npx * Tl.tc[0].res[r].npy != 0;
+    if (!any) return 0;
+    std::vector<uint32_t> first;
+    return tile_part_runs(P, t, letters, nullptr, first);
 }
 
-int64_t tile_parts_in(const Plan &P, int tile0, int tile1) {
+int64_t tile_parts_in(const Plan &P, int tile0, int tile1, int letters) {
     int64_t n = 0;
-    for (int t = tile0; t < tile1; t++) n += tile_part_count(P, t);
+    for (int t = tile0; t < tile1; t++) n += tile_part_count(P, t, letters);
     return n;
 }
 
-void tile_part_order(const Plan &P, int tile0, int tile1, std::vector<uint16_t> &tiles) {
+void tile_part_order(const Plan &P, int tile0, int tile1, std::vector<uint16_t> &tiles, int letters) {
     tiles.clear();
     std::vector<int> count((size_t)std::max(0, tile1 - tile0));
-    for (int t = tile0; t < tile1; t++) count[(size_t)(t - tile0)] = tile_part_count(P, t);
-    const std::vector<int> ends = flush_stripe_ends(P.nty, P.rc.tile_h, P.h, P.rc.flush_period);
-    int ty0 = 0;
-    for (int e : ends) {  // (the loop t2_tables orders T.tp with)
-        const int a = std::max(tile0, ty0 * P.ntx), b = std::min(tile1, e * P.ntx);
-        for (int k = 0; k <= P.rc.levels; k++)
-            for (int t = a; t < b; t++)
-                if (k < count[(size_t)(t - tile0)]) tiles.push_back((uint16_t)t);
-        ty0 = e;
-    }
+    for (int t = tile0; t < tile1; t++) count[(size_t)(t - tile0)] = tile_part_count(P, t, letters);
+    file_order(P, tile0, tile1, count, [&](int t, int) { tiles.push_back((uint16_t)t); });
+}
+
+int64_t tile_part_division_bytes(const Plan &P, int letters, int64_t ntp) {
+    if (!letters) return 0;
+    return (14 + (P.rc.plt ? 5 : 0)) * (ntp - tile_parts_in(P, 0, P.ntx * P.nty, 0));
 }
 
 int64_t tlm_bytes(int64_t ntp) {

@@ -9,7 +9,9 @@
 // Another progression order (LRCP, RLCP, PCRL, CPRL) changes no packet and
 // no storage index: the tile-part kernels (tpart_size, k_t2_tp_emit) take
 // the packets in the order of the forward map T2Args::seq, and a packet's
-// Nsop is PrecDesc's nsop0 + layer * nsop_step.
+// Nsop is PrecDesc's nsop0 + layer * nsop_step.  A tile-part is a run of its
+// tile's sequence (TpDesc s0, ns: ORGtparts R, L, C cut it on the host,
+// t2.cpp tile_part_runs), its TPsot and TNsot come from the table.
 //
 // Parallel structure.  A precinct's L packets share state (tag trees, each
 // block's Lblock and inclusion layer); precincts are independent (C2: 2 880
@@ -64,9 +66,9 @@ struct T2Args {
     uint32_t *tt;           // tag-tree nodes: value | low << 8 | known << 16
     int8_t *lblock, *incl;  // per block coding state
     uint32_t *pk_len;       // [nprec * L] SOP + header + EPH + body
-    // the progression order's forward map (T2Tables::seq): the s-th packet of
-    // the tile-part whose packets are stored at [p0, p1) is packet seq[p0 + s];
-    // null = RPCL, where it is packet p0 + s
+    // the progression order's forward map (T2Tables::seq): the tile-part that
+    // takes the places [p0, p1) of it (TpDesc s0, ns) sends packet seq[p0 + s]
+    // as its s-th; null = RPCL, where it is packet p0 + s
     const uint32_t *seq;
     uint32_t *tp_len;       // [ntp] Psot
     uint32_t *tp_hdr;       // [ntp] SOT + PLT + SOD
@@ -706,7 +708,7 @@ __device__ __forceinline__ void seq_load8(const T2Args &a, size_t i0, size_t p1,
 template <bool SEQ>
 __device__ __forceinline__ void tpart_size_seq(const T2Args &a, int t) {
     const TpDesc d = a.tps[t];
-    const size_t p0 = (size_t)d.prec0 * a.L, p1 = (size_t)(d.prec0 + d.nprec) * a.L;
+    const size_t p0 = d.s0, p1 = (size_t)d.s0 + d.ns;  // its run of the sequence
     uint64_t body = 0, plt = 0, seg = 0;
     for (size_t i0 = p0; i0 < p1; i0 += 8) {  // 8 lengths' loads in flight at a time
         size_t s8[8];
@@ -919,7 +921,7 @@ __device__ __forceinline__ void tpart_emit(const T2Args &a, int t) {
     p[10] = (uint8_t)d.tpsot;
     p[11] = (uint8_t)d.tnsot;
     p += 12;
-    const size_t p0 = (size_t)d.prec0 * a.L, p1 = (size_t)(d.prec0 + d.nprec) * a.L;
+    const size_t p0 = d.s0, p1 = (size_t)d.s0 + d.ns;  // its run of the sequence
     // packet lengths are loaded 8 at a time ahead of the byte stores (a load
     // after a byte store would wait for it: the stores may alias)
     if (a.plt && p1 > p0) {  // PLT segments (A.7.3): lengths as 7-bit groups, <= 65532 bytes each
@@ -1338,11 +1340,14 @@ bool GpuEncoder::t2_load(const Plan &plan, const T2Tables &T, std::string &err) 
         if (!ensure<uint32_t>(t2ticket, 1, err)) return false;
         HIPCHECK(hipMemsetAsync(t2ticket.ptr, 0, sizeof(uint32_t), stream));
     }
-    if (plan.gen && plan.gen == t2_gen) {  // resident (same plan, same tables)
+    // resident: the same plan cut into tile-parts by the same letters (the
+    // tables' TpDesc depend on them; the plan does not)
+    if (plan.gen && plan.gen == t2_gen && T.letters == t2_letters) {
         reuse |= JP2HIP_REUSED_T2_TABLES;
         return true;
     }
     t2_gen = 0;
+    t2_letters = T.letters;
     if (!h2d(t2prec.ptr, T.prec.data(), sizeof(PrecDesc) * T.prec.size(), err) ||
         !h2d(t2tp.ptr, T.tp.data(), sizeof(TpDesc) * T.tp.size(), err) ||
         (t2_seq && !h2d(t2seq.ptr, T.seq.data(), sizeof(uint32_t) * T.seq.size(), err)))

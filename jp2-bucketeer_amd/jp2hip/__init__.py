@@ -5,7 +5,7 @@
 """
 from ._lib import (FORMAT_J2K, FORMAT_JP2, FORMAT_JPX, LOSSLESS, LOSSY, ORDER_CPRL, ORDER_LRCP, ORDER_PCRL,
                    ORDER_RLCP, ORDER_RPCL, Encoder, Jp2hipError, Output, device_count, device_ordinals,
-                   encoded_format, file_header, packet_sequence, probe, recipe, tiff_layout, tlm_segments, version)
+                   encoded_format, file_header, packet_sequence, probe, recipe, tiff_layout, tile_parts, tlm_segments, version)
 from .converters import (Conversion, Converter, ConverterFactory, GpuConverter,
                          KakaduConverter, KakaduNotFoundError, OpenJPEGConverter)
 
@@ -13,4 +13,4 @@ __all__ = ["Conversion", "Converter", "ConverterFactory", "GpuConverter", "Kakad
            "KakaduNotFoundError", "OpenJPEGConverter", "Encoder", "Jp2hipError", "LOSSY",
            "LOSSLESS", "FORMAT_J2K", "FORMAT_JP2", "FORMAT_JPX", "ORDER_LRCP", "ORDER_RLCP", "ORDER_RPCL",
            "ORDER_PCRL", "ORDER_CPRL", "Output", "device_count", "device_ordinals", "encoded_format",
-           "file_header", "packet_sequence", "probe", "recipe", "tiff_layout", "tlm_segments", "version"]
+           "file_header", "packet_sequence", "probe", "recipe", "tiff_layout", "tile_parts", "tlm_segments", "version"]

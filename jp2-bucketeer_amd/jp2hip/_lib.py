@@ -140,6 +140,8 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            "jp2hip_packet_sequence",
            # code-stream organisation: TLM marker segments (api.cpp, batch.cpp; jp2hip_tlm_segments host only)
            "jp2hip_set_organisation", "jp2hip_batch_set_organisation", "jp2hip_tlm_segments",
+           # tile-part divisions L and C (api.cpp, batch.cpp; jp2hip_tile_parts host only)
+           "jp2hip_set_tile_part_divisions", "jp2hip_batch_set_tile_part_divisions", "jp2hip_tile_parts",
            # device-memory policy (api.cpp; csrc/context.h EncodeEnd)
            "jp2hip_device_bytes", "jp2hip_set_memory_limits", "jp2hip_device_memory", "jp2hip_dma_engines")
 
@@ -206,6 +208,11 @@ def lib():
     L.jp2hip_batch_set_organisation.argtypes = [c_void_p, POINTER(Organisation)]
     L.jp2hip_tlm_segments.argtypes = [POINTER(ctypes.c_uint16), POINTER(c_uint32), c_int64, c_void_p, c_size_t]
     L.jp2hip_tlm_segments.restype = c_int64
+    L.jp2hip_set_tile_part_divisions.argtypes = [c_void_p, c_int32]
+    L.jp2hip_batch_set_tile_part_divisions.argtypes = [c_void_p, c_int32]
+    L.jp2hip_tile_parts.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(Recipe), c_int32, c_int32,
+                                    POINTER(c_uint32), c_int64]
+    L.jp2hip_tile_parts.restype = c_int64
     L.jp2hip_device_bytes.argtypes = [c_void_p]
     L.jp2hip_device_bytes.restype = c_int64
     L.jp2hip_set_memory_limits.argtypes = [c_void_p, c_int64, c_int64]
@@ -307,6 +314,37 @@ def packet_sequence(width: int, height: int, components: int, bits: int, rcp: Re
         raise Jp2hipError(last_error())
     buf = (c_uint32 * max(1, n))()
     if int(lib().jp2hip_packet_sequence(width, height, components, bits, byref(rcp), tile, buf, n)) != n:
+        raise Jp2hipError(last_error())
+    return list(buf[:n])
+
+
+TPARTS_L, TPARTS_C = 2, 4  # JP2HIP_TPARTS_L, JP2HIP_TPARTS_C
+
+
+def tparts_letters(letters) -> int:
+    """"L", "C", "LC" (any case and order; "" = none) or the bits themselves
+    as the int jp2hip_set_tile_part_divisions takes.  "R" maps to bit 1, which
+    the library refuses with a pointer at ``Recipe.tparts_r``."""
+    if isinstance(letters, str):
+        bits = {"R": 1, "L": TPARTS_L, "C": TPARTS_C}
+        unknown = [ch for ch in letters.upper() if ch not in bits]
+        if unknown:
+            raise ValueError(f"tile-part divisions: {letters!r} has letters other than L and C")
+        return sum({bits[ch] for ch in letters.upper()})
+    return int(letters)
+
+
+def tile_parts(width: int, height: int, components: int, bits: int, rcp: Recipe, letters, tile: int) -> list[int]:
+    """The tile-parts of tile `tile` under ``rcp`` and the divisions `letters`
+    (jp2hip_tile_parts; no GPU): the place in the tile's packet_sequence at
+    which each starts, so their count is the list's length.  Raises for
+    anything the encodes refuse (more than 255 tile-parts in a tile too)."""
+    bits_ = tparts_letters(letters)
+    n = int(lib().jp2hip_tile_parts(width, height, components, bits, byref(rcp), bits_, tile, None, 0))
+    if n < 0:
+        raise Jp2hipError(last_error())
+    buf = (c_uint32 * max(1, n))()
+    if int(lib().jp2hip_tile_parts(width, height, components, bits, byref(rcp), bits_, tile, buf, n)) != n:
         raise Jp2hipError(last_error())
     return list(buf[:n])
 
@@ -463,6 +501,14 @@ class Encoder:
         (ORGgen_tlm).  Not while the context is encoding."""
         org = Organisation(int(tlm), (c_int32 * 3)(*reserved))
         if lib().jp2hip_set_organisation(self._h, byref(org)) != 0:
+            raise Jp2hipError(last_error())
+
+    def set_tile_part_divisions(self, letters=0):
+        """jp2hip_set_tile_part_divisions, for every later encode on this
+        context and its tile-split peers: "L", "C", "LC" or the bits
+        (TPARTS_L | TPARTS_C); 0 restores the output without them.  R stays
+        ``Recipe.tparts_r``.  Not while the context is encoding."""
+        if lib().jp2hip_set_tile_part_divisions(self._h, tparts_letters(letters)) != 0:
             raise Jp2hipError(last_error())
 
     def _take(self, out, n, copy=True):

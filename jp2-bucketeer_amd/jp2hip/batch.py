@@ -63,7 +63,8 @@ class BatchResult(Structure):
 UPLOAD_FN = CFUNCTYPE(c_int, c_void_p, c_char_p, c_char_p)
 
 BATCH_EXPORTS = ("jp2hip_batch_create", "jp2hip_batch_submit", "jp2hip_batch_wait",
-                 "jp2hip_batch_pending", "jp2hip_batch_destroy", "jp2hip_batch_set_organisation")
+                 "jp2hip_batch_pending", "jp2hip_batch_destroy", "jp2hip_batch_set_organisation",
+                 "jp2hip_batch_set_tile_part_divisions")
 
 
 def _bind():
@@ -78,6 +79,7 @@ def _bind():
     L.jp2hip_batch_pending.restype = c_int64
     L.jp2hip_batch_destroy.argtypes = [c_void_p]
     L.jp2hip_batch_set_organisation.argtypes = [c_void_p, POINTER(_lib.Organisation)]
+    L.jp2hip_batch_set_tile_part_divisions.argtypes = [c_void_p, c_int32]
     L._batch_bound = True
     return L
 
@@ -242,6 +244,12 @@ class BatchQueue:
         context of the queue; only before the first submit."""
         org = _lib.Organisation(int(tlm), (c_int32 * 3)(*reserved))
         if _bind().jp2hip_batch_set_organisation(self._h, byref(org)) != 0:
+            raise _lib.Jp2hipError(_lib.last_error() or "the queue has taken a job already")
+
+    def set_tile_part_divisions(self, letters=0):
+        """jp2hip_batch_set_tile_part_divisions: Encoder.set_tile_part_divisions
+        on every context of the queue; only before the first submit."""
+        if _bind().jp2hip_batch_set_tile_part_divisions(self._h, _lib.tparts_letters(letters)) != 0:
             raise _lib.Jp2hipError(_lib.last_error() or "the queue has taken a job already")
 
     def submit(self, job: int, image_id: str, tiff: os.PathLike | str, jpx: os.PathLike | str,
