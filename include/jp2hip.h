@@ -343,6 +343,66 @@ int64_t jp2hip_tile_parts(int32_t width, int32_t height, int32_t components, int
 int64_t jp2hip_tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n,
                             uint8_t *dst, size_t cap);
 
+/* Fixed-slope quality layers (Kakadu's -slope s1,s2,...): with n =
+ * recipe.layers thresholds set, layer 0 first, an encode has no byte target and
+ * no rate loop -- layer l holds, per code-block, the passes of the block's
+ * convex hull whose distortion-length slope is >= slopes[l].  A threshold is a
+ * slope in the library's own units: the double whose bit pattern is the PCRD
+ * slope key (squared error in sample units, weighted by the band's synthesis
+ * gain, per byte); Kdu-Layer-Info prints log2 of it less 2 * bits
+ * (jp2hip_slope_to_log2).  +0.0 takes the whole hull, +inf takes nothing.
+ * NULL / n = 0 turns it off (the encodes are again rate-driven or lossless).
+ *   - With slopes set, recipe.rate_bpp > 0 only selects the irreversible
+ *     recipe's meaning of "not lossless": its value is no target.  With
+ *     rate_bpp <= 0 the last layer takes every coded pass, as without slopes,
+ *     and its threshold must be 0.
+ *   - recipe.slope_skip is ignored: every bit-plane is coded.
+ *   - stats.rate_iterations = 0; the TLM's T and the tile-part divisions' E
+ *     lower nothing, no target exists.
+ *   - The Kdu-Layer-Info lines print the given thresholds.
+ *   - The slopes are no part of the plan cache's key.
+ *   - Over a caller's callback a tile-split is collective in the slopes as it
+ *     is in the organisation: every rank sets the same ones (peers of
+ *     jp2hip_split_peers get them here and inherit them when added later).
+ * Refused, with a message that names the entry: a NaN, a negative value, a
+ * sequence that increases anywhere, n outside 0..32; at the encode, n other
+ * than the recipe's layers and, with rate_bpp <= 0, a last entry other than 0
+ * (the context stays usable).  Not to be called while ctx is encoding. */
+int jp2hip_set_layer_slopes(jp2hip_ctx *ctx, const double *slopes, int32_t n);
+
+/* Host-only, for tests and callers: the checks above on their own -- those of
+ * the encode too when `recipe` is given.  Returns 0, or < 0 with a message
+ * that names the entry. */
+int jp2hip_check_layer_slopes(const double *slopes, int32_t n, const jp2hip_recipe *recipe);
+
+/* Kdu-Layer-Info's number <-> a threshold for `bits`-bit samples:
+ * s = 2^(v + 2 * bits). */
+double jp2hip_slope_from_log2(double v, int32_t bits);
+double jp2hip_slope_to_log2(double s, int32_t bits);
+
+/* What the layers of the last successful encode on ctx came to (any encode,
+ * with slopes or without).  The struct has a tag only, no typedef: the tag
+ * shares its name with the function that fills it, which C and C++ allow a
+ * tag but not a typedef, so it is written `struct jp2hip_layer_report`. */
+struct jp2hip_layer_report {
+    int32_t layers, distortion_valid;
+    double  threshold[32];   /* the slope each layer was cut at (what the COM prints, before log2) */
+    int64_t bytes[32];       /* code-stream bytes through the layer (the COM's L column)          */
+    double  distortion[32];  /* predicted squared error left after the layer, sample units,
+                                summed over the image; NaN unless enabled                         */
+};
+/* on = 1: every later encode on ctx (and its tile-split peers) also sums, on
+ * the device and after its final selection, the distortion each layer leaves:
+ * over the code-blocks, the band's weight times the squared-error decrease of
+ * the coding passes the layer does not hold.  Exact (against a decoder's
+ * summed squared error) where the transform is orthogonal -- levels = 0 --
+ * and an estimate otherwise.  Deterministic: two runs of one
+ * encode on one route give equal bits.  Default 0: nothing is launched. */
+int jp2hip_set_layer_report(jp2hip_ctx *ctx, int32_t on);
+/* Copies the report; < 0 when no encode on ctx has succeeded yet.  After a
+ * tile-split over a caller's callback only rank 0's report is whole. */
+int jp2hip_layer_report(jp2hip_ctx *ctx, struct jp2hip_layer_report *r);
+
 /* Which SDMA engines the code-stream copies use, per GPU probed so far, and
  * every engine's measured device -> host rate ("" before the first encode):
  * engines differ several-fold on MI355X and the choice is timed once per
@@ -575,6 +635,9 @@ int jp2hip_batch_set_organisation(jp2hip_batch *b, const jp2hip_organisation *or
 /* jp2hip_set_tile_part_divisions on every context of the queue; before the
  * first submit (< 0 after it, or for refused letters). */
 int jp2hip_batch_set_tile_part_divisions(jp2hip_batch *b, int32_t letters);
+/* jp2hip_set_layer_slopes on every context of the queue; before the first
+ * submit (< 0 after it, or for refused slopes). */
+int jp2hip_batch_set_layer_slopes(jp2hip_batch *b, const double *slopes, int32_t n);
 /* Queue one image: convert `tiff_path` into `jpx_path` (written atomically)
  * with `conversion` (recipe NULL -> Bucketeer recipe), then upload it under
  * `image_id`.  Never blocks on the GPU; returns < 0 after close. */

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -287,6 +288,43 @@ int jp2hip_set_tile_part_divisions(jp2hip_ctx *ctx, int32_t letters) {
     return 0;
 }
 
+int jp2hip_check_layer_slopes(const double *slopes, int32_t n, const jp2hip_recipe *recipe) {
+    std::string err;
+    return jp2hip::check_layer_slopes(slopes, n, recipe, err) ? 0 : fail(err);
+}
+
+int jp2hip_set_layer_slopes(jp2hip_ctx *ctx, const double *slopes, int32_t n) {
+    if (!slopes) n = 0;
+    if (jp2hip_check_layer_slopes(slopes, n, nullptr) != 0) return -1;
+    if (!ctx) return fail("null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->slopes.assign(slopes, slopes + n);
+    for (jp2hip_ctx *p : ctx->peers)
+        if (jp2hip_set_layer_slopes(p, slopes, n) != 0) return -1;
+    return 0;
+}
+
+double jp2hip_slope_from_log2(double v, int32_t bits) { return std::exp2(v + 2.0 * bits); }
+double jp2hip_slope_to_log2(double s, int32_t bits) { return std::log2(s) - 2.0 * bits; }
+
+int jp2hip_set_layer_report(jp2hip_ctx *ctx, int32_t on) {
+    if (on != 0 && on != 1) return fail("layer report: on must be 0 or 1, not " + std::to_string(on));
+    if (!ctx) return fail("null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->report_on = on;
+    for (jp2hip_ctx *p : ctx->peers)
+        if (jp2hip_set_layer_report(p, on) != 0) return -1;
+    return 0;
+}
+
+int jp2hip_layer_report(jp2hip_ctx *ctx, struct jp2hip_layer_report *r) {
+    if (!ctx || !r) return fail("null argument");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->report_set) return fail("layer report: no encode on this context has written a main header yet");
+    *r = ctx->report;
+    return 0;
+}
+
 int64_t jp2hip_tile_parts(int32_t width, int32_t height, int32_t components, int32_t bits,
                           const jp2hip_recipe *recipe, int32_t letters, int32_t tile, uint32_t *first, int64_t cap) {
     if (!recipe || cap < 0 || (cap > 0 && !first)) return fail("null recipe, or no room for the tile-parts");
@@ -497,6 +535,8 @@ int jp2hip_split_peers(jp2hip_ctx *ctx, const int32_t *ordinals, int32_t n, int6
         }
         p->org = ctx->org;  // (jp2hip_set_organisation: peers added later inherit it)
         p->tparts = ctx->tparts;  // (jp2hip_set_tile_part_divisions likewise)
+        p->slopes = ctx->slopes;  // (jp2hip_set_layer_slopes, jp2hip_set_layer_report likewise)
+        p->report_on = ctx->report_on;
         made.push_back(p);
     }
     for (jp2hip_ctx *p : ctx->peers) jp2hip_destroy(p);

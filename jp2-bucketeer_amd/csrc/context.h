@@ -46,6 +46,13 @@ struct jp2hip_ctx {
     // jp2hip_set_tile_part_divisions: JP2HIP_TPARTS_L | _C, read by every
     // encode; the tier-2 tables depend on it, the plan does not
     int32_t tparts = 0;
+    // jp2hip_set_layer_slopes: the layers' thresholds (empty: off), read by
+    // every encode, no part of the plan cache's key; jp2hip_set_layer_report
+    // and what the last successful encode's layers came to
+    std::vector<double> slopes;
+    int32_t report_on = 0;
+    bool report_set = false;
+    struct jp2hip_layer_report report{};
     // tile-split members (jp2hip_split_peers): images of at least
     // split_min_pixels are encoded by this context (rank 0) and these
     // (ranks 1..), owned here

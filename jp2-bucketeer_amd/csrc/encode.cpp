@@ -7,6 +7,8 @@
 // decision-stream pool was short; the benchmark measures this one), the split
 // encode iterates on the host over thresholds its ranks exchange, its pool
 // sized for the worst case (pool_worst: ranks cannot repeat an exchange).
+// With fixed-slope layers (jp2hip_set_layer_slopes) neither runs: both encodes
+// apply the caller's thresholds where the lossless encode applies its own.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -58,7 +60,43 @@ jp2hip_recipe recipe_of(const jp2hip_recipe *recipe, int conversion) {
     return rc;
 }
 
+bool check_layer_slopes(const double *s, int n, const jp2hip_recipe *rc, std::string &err) {
+    if (n < 0 || n > kMaxLayers || (n > 0 && !s)) {
+        err = "layer slopes: n = " + std::to_string(n) + " is outside 0 .. " + std::to_string(kMaxLayers) +
+              " (or no thresholds were given)";
+        return false;
+    }
+    for (int i = 0; i < n; i++) {
+        const std::string at = "layer slopes: slopes[" + std::to_string(i) + "]";
+        if (std::isnan(s[i])) err = at + " is NaN";
+        else if (std::signbit(s[i])) err = at + " = " + std::to_string(s[i]) + " is negative";
+        else if (i && s[i] > s[i - 1])
+            err = at + " increases over slopes[" + std::to_string(i - 1) + "]: the thresholds fall from layer 0 on";
+        else continue;
+        return false;
+    }
+    if (!rc || !n) return true;
+    if (n != rc->layers) {
+        err = "layer slopes: n = " + std::to_string(n) + " thresholds for an encode of recipe.layers = " +
+              std::to_string(rc->layers);
+        return false;
+    }
+    if (rc->rate_bpp <= 0.0 && s[n - 1] != 0.0) {
+        err = "layer slopes: slopes[" + std::to_string(n - 1) + "], the last, must be 0 with rate_bpp <= 0 " +
+              "(the last layer takes every coded pass)";
+        return false;
+    }
+    return true;
+}
+
 namespace {
+
+// The slope keys of a context's thresholds: the doubles' bit patterns.
+std::vector<uint64_t> slope_keys(const std::vector<double> &s) {
+    std::vector<uint64_t> K(s.size());
+    if (!s.empty()) std::memcpy(K.data(), s.data(), 8 * s.size());
+    return K;
+}
 
 // A rate-driven encode's target (bytes): the floor(rate * W * H / 8) the
 // oracle's predict_and_code uses; slope prediction's is the same, -1 = off
@@ -94,6 +132,9 @@ int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conv
     if (!lay || !d_src) return fail("null source or layout");
     std::string terr;  // tile_w = tile_h = 0: one tile for this image
     if (!resolve_tiles(rc, lay->width, lay->height, terr)) return fail(terr);
+    // fixed-slope layers: the thresholds against this encode's recipe (refused
+    // before the encode begins: the context stays as it was)
+    if (!check_layer_slopes(ctx->slopes.data(), (int)ctx->slopes.size(), &rc, terr)) return fail(terr);
     meta = source_meta(*lay);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
     ctx->gpu.take_waits();     // count this encode's host waits (stats)
     ctx->gpu.begin_encode();
@@ -124,13 +165,16 @@ struct FilePart {
 // failure) and hands it to the caller with the encode's stats.  K: the final
 // selection's slope keys; tp_hdr, layer_bytes, cs_bytes: whole-image sums
 // (Kdu-Layer-Info, the file header's code-stream length); file_bytes: the
-// whole file.
+// whole file; dist: the layer report's whole-image distortions (null: not
+// enabled).  The rank that writes the main header keeps the layer report.
 int finish_part(jp2hip_ctx *ctx, const FilePart &fp, const SourceMeta &meta, std::vector<uint64_t> K, int64_t tp_hdr,
                 const int64_t *layer_bytes, int64_t cs_bytes, const T2Summary &sum, uint8_t *buf, StageTimes &st,
                 uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start, double h2d_ms,
-                int64_t file_bytes, int iters) {
+                int64_t file_bytes, int iters, const double *dist) {
     const Plan &P = fp.file;
     std::string err;
+    struct jp2hip_layer_report rep;  // kept on success
+    std::memset(&rep, 0, sizeof rep);
     if (fp.with_main) {
         // Kdu-Layer-Info: the slope keys (lossless: the last layer takes
         // every pass) and the code-stream bytes through each layer
@@ -141,6 +185,15 @@ int finish_part(jp2hip_ctx *ctx, const FilePart &fp, const SourceMeta &meta, std
         for (int l = 0; l < L; l++) layer_end[l] = acc += layer_bytes[l];
         std::vector<uint8_t> mh;
         main_header(P, mh, K.data(), layer_end.data());
+        struct jp2hip_layer_report &r = rep;
+        r.layers = L;
+        r.distortion_valid = dist != nullptr;
+        for (int l = 0; l < L; l++) {
+            if (K[l] >= 0x7FF0000000000000ull) r.threshold[l] = HUGE_VAL;  // nothing taken
+            else std::memcpy(&r.threshold[l], &K[l], 8);
+            r.bytes[l] = layer_end[l];
+            r.distortion[l] = dist ? dist[l] : std::nan("");
+        }
         write_file_header(P, meta, (uint64_t)cs_bytes, buf);
         std::memcpy(buf + fp.fh, mh.data(), mh.size());
         if (fp.tlm_host) std::memcpy(buf + fp.head - fp.tlm, fp.tlm_host, fp.tlm);
@@ -159,6 +212,8 @@ int finish_part(jp2hip_ctx *ctx, const FilePart &fp, const SourceMeta &meta, std
     }
     *out = buf;
     *out_len = fp.bytes;
+    ctx->report = rep;
+    ctx->report_set = fp.with_main;
     if (!stats) return 0;
     std::memset(stats, 0, sizeof *stats);
     stats->total_ms = now_ms() - t_start;
@@ -239,7 +294,11 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     if (ctx->org.tlm && (int64_t)pc.tabs.tp.size() > kTlmMaxEntries)
         return fail("tlm: more tile-parts than 256 TLM marker segments hold");
     const int64_t E = pc.division_bytes;  // what the L / C divisions add
-    int64_t skip_target = skip_target_of(rc, plan.w, plan.h, tlm + E);
+    // fixed-slope layers (jp2hip_set_layer_slopes): no target, so nothing is
+    // predicted and every plane is coded
+    const bool fixed = !ctx->slopes.empty();
+    const std::vector<uint64_t> keys = slope_keys(ctx->slopes);
+    int64_t skip_target = fixed ? -1 : skip_target_of(rc, plan.w, plan.h, tlm + E);
     // tier-2 tables first: every host->device copy of the encode is issued
     // while the stream is idle (a copy queued behind kernels holds up the
     // copy engine for the other contexts)
@@ -250,11 +309,14 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     std::memset(&sum, 0, sizeof sum);
     int iters = 0;
     int64_t cs_bytes = 0;
-    if (rc.rate_bpp <= 0.0) {
+    if (fixed || rc.rate_bpp <= 0.0) {
         // lossless: per -flush_period stripe, layer l keeps the passes whose
-        // slopes clear lossless_layer_frac(l) of the stripe's tier-1 bytes
+        // slopes clear lossless_layer_frac(l) of the stripe's tier-1 bytes;
+        // fixed slopes: layer l keeps the passes whose slopes clear the
+        // caller's threshold, in every stripe (no target, no rate loop)
         for (int grow = 0;; grow++) {
-            if (!ctx->gpu.select_lossless(plan, err) || !ctx->gpu.t2_size(plan, true, prof, st, sum, err))
+            if (!(fixed ? ctx->gpu.select_keys(plan, keys, err) : ctx->gpu.select_lossless(plan, err)) ||
+                !ctx->gpu.t2_size(plan, true, prof, st, sum, err))
                 return fail(err);
             if ((sum.err & kErrSlotPool) && grow < 2) {
                 // the decision-stream pool was short: again with the size
@@ -266,7 +328,7 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
             break;
         }
         if (sum.err) return fail("tier-1 output capacity exceeded");
-        iters = 1;
+        iters = fixed ? 0 : 1;
         cs_bytes = (int64_t)mh_bytes + tlm + sum.part_bytes + 2;
     } else {
         // the rate loop runs on the device (GpuEncoder::rate_loop): one
@@ -309,13 +371,16 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         iters = rs.iters;
         cs_bytes = rs.cs_bytes + tlm + E;  // (rs.cs_bytes = init.fixed + sum.part_bytes: device_common.h rate_step)
     }
+    // the layer report's distortion, after the final selection (enabled only)
+    double dist[kMaxLayers];
+    if (ctx->report_on && !ctx->gpu.layer_dist(plan, dist, err)) return fail(err);
     FilePart fp{plan, plan, true, true, true};
     fp.size(meta, mh_bytes, sum.part_bytes, (size_t)tlm);
     uint8_t *buf = out_alloc(fp.bytes);
     if (!buf) return fail("out of (pinned) host memory");
     if (finish_part(ctx, fp, meta, std::vector<uint64_t>(sum.kc, sum.kc + rc.layers), sum.tp_hdr_bytes,
                     sum.layer_bytes, cs_bytes, sum, buf, st, out, out_len, stats, t_start, h2d_ms, (int64_t)fp.bytes,
-                    iters))
+                    iters, ctx->report_on ? dist : nullptr))
         return -1;
     end.ok = true;
     return 0;
@@ -403,7 +468,10 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // slope prediction over the whole image: the plane histogram is summed
     // over ranks (one all-reduce of kSlopeBins + 1 int64, the last a failure
     // flag, so a rank that failed earlier still joins the exchange)
-    int64_t skip_target = skip_target_of(rc, full.w, full.h, tlm + E);
+    // fixed-slope layers (collective, like the organisation): no target,
+    // nothing predicted, no threshold exchange
+    const bool fixed = !ctx->slopes.empty();
+    int64_t skip_target = fixed ? -1 : skip_target_of(rc, full.w, full.h, tlm + E);
     bool hist_done = false;
     GpuEncoder::HistReduce reduce = [&](std::vector<int64_t> &h) {
         hist_done = true;
@@ -440,9 +508,10 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // sizing pass, its sums exchanged: [0] part bytes, [1] failure flag, [2]
     // tile-part header bytes, [3..] packet bytes per layer (Kdu-Layer-Info),
     // then, lossless, L slope keys per rank.  False on failure (err).
-    auto round = [&](bool lossless) -> bool {
-        if (!lossless && jp2hip_split_thresholds(keys.data(), cum.data(), (int64_t)keys.size(), budgets.data(), L, sp,
-                                                 K.data()) != 0) {
+    // fixed_keys: K holds the caller's thresholds, nothing about them is exchanged.
+    auto round = [&](bool lossless, bool fixed_keys = false) -> bool {
+        if (!lossless && !fixed_keys &&
+            jp2hip_split_thresholds(keys.data(), cum.data(), (int64_t)keys.size(), budgets.data(), L, sp, K.data()) != 0) {
             err = "split: threshold exchange failed";
             return false;
         }
@@ -475,6 +544,12 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         return true;
     };
     for (int attempt = 0; attempt < 2; attempt++) {
+        if (fixed) {
+            K = slope_keys(ctx->slopes);
+            if (!round(false, true)) return fail(err);
+            iters = 0;
+            break;
+        }
         if (attempt == 1) {  // the prediction's safety net, decided globally (below)
             keys.clear();
             cum.clear();
@@ -510,6 +585,23 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
             budget -= ((cs_bytes - target) << it) + ((cs_bytes - target) >> 4) + 64;
         }
         if (!rerun) break;
+    }
+    // the layer report's distortion (collective in jp2hip_set_layer_report):
+    // every rank's sums travel in its own slots of one exchange as bit
+    // patterns, zeros elsewhere, and are added here in rank order
+    double dist[kMaxLayers] = {};
+    if (ctx->report_on) {
+        double mine[kMaxLayers] = {};
+        bool dok = !have || ctx->gpu.layer_dist(sub, mine, err);
+        std::vector<int64_t> v((size_t)world * L + 1, 0);
+        if (dok && have) std::memcpy(&v[(size_t)rank * L], mine, 8 * (size_t)L);
+        if (!exchange(v, (size_t)world * L, dok) || !dok) return fail(err);
+        for (int r = 0; r < world; r++)
+            for (int l = 0; l < L; l++) {
+                double d;
+                std::memcpy(&d, &v[(size_t)r * L + l], 8);
+                dist[l] += d;
+            }
     }
     // this rank's part of the file.  Everything its emission allocates is
     // allocated before the ranks agree on the part sizes, so a rank that
@@ -572,7 +664,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     }
     cs_bytes += tlm + E;
     if (finish_part(ctx, fp, meta, K, g_tp_hdr, g_layer.data(), cs_bytes, sum, buf, st, out, out_len, stats, t_start,
-                    0.0, (int64_t)flen, iters))
+                    0.0, (int64_t)flen, iters, ctx->report_on ? dist : nullptr))
         return -1;
     if (file_offset) *file_offset = off;
     if (file_len) *file_len = flen;

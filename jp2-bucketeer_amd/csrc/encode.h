@@ -23,6 +23,10 @@ bool prepare_source(jp2hip_ctx *ctx, const UnitGrid &g, const void *&d_src, size
 // encode.cpp (the caller holds ctx->mu)
 void default_recipe(jp2hip_recipe *r, int conversion);
 jp2hip_recipe recipe_of(const jp2hip_recipe *recipe, int conversion);
+// jp2hip_set_layer_slopes' thresholds: a NaN, a negative value and a sequence
+// that increases are refused; with rc (the encode's recipe) also n other than
+// rc->layers and, lossless, a last entry other than 0.  err names the entry.
+bool check_layer_slopes(const double *slopes, int n, const jp2hip_recipe *rc, std::string &err);
 int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
                 const jp2hip_recipe *recipe, uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start,
                 double h2d_ms);

@@ -98,6 +98,7 @@ GpuEncoder::~GpuEncoder() {
     if (h_sum) (void)hipHostFree(h_sum);
     if (h_tot) (void)hipHostFree(h_tot);
     if (h_rs) (void)hipHostFree(h_rs);
+    if (h_dist) (void)hipHostFree(h_dist);
     if (dma_dep.handle) (void)hsa_signal_destroy(dma_dep);
     if (dma_done.handle) (void)hsa_signal_destroy(dma_done);
     if (hsa_up) (void)hsa_shut_down();

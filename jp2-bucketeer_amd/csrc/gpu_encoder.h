@@ -49,7 +49,9 @@ struct FrontJob;  // front.hip
     X(hdist) X(rstate) X(t2ticket) X(t2prec) X(t2tp) X(t2tt) X(t2lblock) X(t2incl) X(t2pklen) X(t2pkoff)      \
     X(t2tplen) X(t2tphdr) X(t2tpoff) X(t2blkdst) X(t2out) X(t2sum) X(t2seq)                                   \
     /* S1b sample expansion (expand.hip): the 8-bit copy, its unit offsets and the colour table */           \
-    X(expanded) X(exoff) X(exlut)
+    X(expanded) X(exoff) X(exlut)                                                                             \
+    /* the layer report's per-workgroup distortion sums and their totals (k_layer_dist) */                   \
+    X(ldist)
 
 // Owns all device memory of a context; buffers only grow while the context
 // stays within its soft limit, so repeated encodes of the same geometry never
@@ -152,7 +154,13 @@ class GpuEncoder {
     bool select_lossless(const Plan &plan, std::string &err);
     // per-block layer tables for explicit slope thresholds K[layer]
     // (tile-split: thresholds agreed across ranks)
+    // (and fixed-slope layers: the caller's own), the same keys for every
+    // rate-control group, shown as K and as Kc (T2Summary::kc)
     bool select_keys(const Plan &plan, const std::vector<uint64_t> &K, std::string &err);
+    // jp2hip_layer_report's distortion: per layer, over the plan's blocks,
+    // weight x the distortion decrease of the passes the final selection
+    // (the thresholds in `thr`) leaves out; d[kMaxLayers]; one host wait
+    bool layer_dist(const Plan &plan, double *d, std::string &err);
     // tier-2 on the device (t2_device.hip): tables for the tiles coded, one sizing
     // pass per layer table (one host wait: the summary), then the code-stream
     // part (tile-parts, in stream order) written in HBM and copied to host_dst
@@ -277,6 +285,7 @@ class GpuEncoder {
     int reuse = 0;                   // reuse_bits() of the current encode
     bool reuse_front_noted = false;  // (its first run_front is the one noted: a repeat finds its own uploads)
     T2Summary *h_sum = nullptr;
+    double *h_dist = nullptr;  // pinned [kMaxLayers]: layer_dist's result
     int64_t *h_tot = nullptr;  // pinned [8]: t1 total, -, k_t1_mq span[2], unpack error, segment tail[2]
     bool profiled = false;
     bool expand_timed = false;  // this encode recorded kEvExpandBegin / End

@@ -2,10 +2,13 @@
 // convex hull of every code-block (k_hull, enqueued by run_front), the slope
 // thresholds of every layer (k_select, k_select_resolve), the per-block layer
 // tables for precincts the wave coder of t2_device.hip does not take
-// (k_apply), and the hull segment list of the tile-split exchange
-// (k_seg_offsets, k_seg_emit).  The GpuEncoder members that launch them
-// follow the kernels: hull_launch, select_launch, select_lossless,
-// select_keys, apply_thresholds, rate_loop, segments.
+// (k_apply), the hull segment list of the tile-split exchange
+// (k_seg_offsets, k_seg_emit), caller-given thresholds for every rate-control
+// group (k_fill_keys: the tile-split's agreed keys and fixed-slope layers) and
+// the layer report's distortion sums (k_layer_dist, k_layer_dist_sum).  The
+// GpuEncoder members that launch them follow the kernels: hull_launch,
+// select_launch, select_lossless, select_keys, layer_dist, apply_thresholds,
+// rate_loop, segments.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -682,6 +685,82 @@ __global__ void __launch_bounds__(256) k_apply(ApplyArgs a) {
     }
 }
 
+// Caller-given thresholds (select_keys): the same L keys for every
+// rate-control group, into the K half and the Kc half of `thr`.  The keys
+// travel as the kernel's argument: no copy is queued.
+struct KeyArgs {
+    int ngroups, layers;
+    uint64_t key[kMaxLayers];
+    uint64_t *thr;  // [2][group][kMaxLayers]
+};
+__global__ void __launch_bounds__(64) k_fill_keys(KeyArgs a) {
+    const int l = threadIdx.x, n = 2 * a.ngroups;
+    if (l >= kMaxLayers) return;
+    for (int g = blockIdx.x; g < n; g += gridDim.x) a.thr[(size_t)g * kMaxLayers + l] = l < a.layers ? a.key[l] : 0ull;
+}
+
+// The layer report's distortion (jp2hip_layer_report): per layer the squared
+// error the layer leaves, summed over the code-blocks -- the block's weight
+// times the distortion decrease of the passes the layer does not hold, total
+// less what the hull's stack recorded at the layer's point (HullPt::d).
+// Thread per block; per layer the wave's 64 values are added by a butterfly,
+// the workgroup's waves in wave order, and the workgroup's sum is stored at
+// part[workgroup][layer]; k_layer_dist_sum adds those in workgroup order.  No
+// floating-point atomics: the same launch gives the same bits.
+struct DistArgs {
+    int nblocks, layers, lossless, ngroups, nparts;
+    const int32_t *grp_b0;
+    const uint8_t *nhull, *npasses;
+    const uint64_t *hkey, *K;
+    const int64_t *dists, *hdist;
+    const double *weight;
+    double *part;  // [nparts][kMaxLayers]
+    double *out;   // [kMaxLayers]
+};
+constexpr int kDistThreads = 256;
+__global__ void __launch_bounds__(kDistThreads) k_layer_dist(DistArgs a) {
+    __shared__ double ws[kDistThreads / 64][kMaxLayers];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int b = blockIdx.x * kDistThreads + tid, L = a.layers;
+    const bool live = b < a.nblocks;
+    const int bb = live ? b : 0;  // (idle lanes read block 0 and contribute 0)
+    const int np = live ? a.npasses[bb] : 0, nh = live ? a.nhull[bb] : 1;
+    const uint64_t *hk = a.hkey + (size_t)bb * (kMaxPasses + 1);
+    const HullPt *hs = (const HullPt *)a.hdist + (size_t)bb * (kMaxPasses + 1);
+    const int64_t *Dd = a.dists + (size_t)bb * kMaxPasses;
+    const uint64_t *K = a.K + (size_t)(live ? block_group(a.grp_b0, a.ngroups, bb) : 0) * kMaxLayers;
+    const double wgt = live ? a.weight[bb] : 0.0;
+    int64_t total = 0;
+    for (int i = 0; i < np; i++) total += Dd[i];
+    for (int l = 0; l < L; l++) {
+        int64_t through = 0;
+        if (a.lossless && l == L - 1) {
+            through = total;
+        } else if (live) {
+            const int at = hull_pick(hk, nh, K[l]);
+            through = at ? hs[at].d : 0;
+        }
+        double v = wgt * (double)(total - through);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        if (lane == 0) ws[wv][l] = v;
+    }
+    __syncthreads();
+    if (tid < L) {
+        double s = ws[0][tid];
+        for (int w = 1; w < kDistThreads / 64; w++) s += ws[w][tid];
+        a.part[(size_t)blockIdx.x * kMaxLayers + tid] = s;
+    }
+}
+__global__ void __launch_bounds__(64) k_layer_dist_sum(DistArgs a) {
+    const int l = threadIdx.x;
+    if (l >= kMaxLayers) return;
+    double s = 0.0;
+    if (l < a.layers)
+        for (int p = 0; p < a.nparts; p++) s += a.part[(size_t)p * kMaxLayers + l];
+    a.out[l] = s;
+}
+
 // --------------------------------------------------------------------------
 // The GpuEncoder members that launch the kernels above
 // --------------------------------------------------------------------------
@@ -782,13 +861,55 @@ bool GpuEncoder::select_lossless(const Plan &plan, std::string &err) {
 
 bool GpuEncoder::select_keys(const Plan &plan, const std::vector<uint64_t> &K, std::string &err) {
     HIPCHECK(hipSetDevice(device));
-    if (plan.ngroups() != 1) {
-        err = "select_keys: one rate-control group expected";
+    const int G = plan.ngroups(), L = plan.rc.layers;
+    if ((int)K.size() < L || L > kMaxLayers) {
+        err = "select_keys: a key per layer expected";
         return false;
     }
-    if (!h2d(thr.ptr, K.data(), sizeof(uint64_t) * plan.rc.layers, err)) return false;
     HIPCHECK(hipEventRecord(ev[kEvSelectBegin], stream));
+    KeyArgs ka;
+    ka.ngroups = G;
+    ka.layers = L;
+    for (int l = 0; l < kMaxLayers; l++) ka.key[l] = l < L ? K[(size_t)l] : 0ull;
+    ka.thr = (uint64_t *)thr.ptr;  // (hull_launch reserved 2 G kMaxLayers keys)
+    if (G > 0) hipLaunchKernelGGL(k_fill_keys, dim3(std::min(2 * G, 1024)), dim3(64), 0, stream, ka);
+    HIPCHECK(hipGetLastError());
     return apply_thresholds(plan, nullptr, err);
+}
+
+// the layer report's distortion for the thresholds in `thr` (the final
+// selection's), one host wait; d: kMaxLayers values, layers .. are 0
+bool GpuEncoder::layer_dist(const Plan &plan, double *d, std::string &err) {
+    HIPCHECK(hipSetDevice(device));
+    const int nb = (int)plan.blocks.size();
+    std::fill(d, d + kMaxLayers, 0.0);
+    if (!nb) return true;
+    const int nparts = (nb + kDistThreads - 1) / kDistThreads;
+    if (!ensure<double>(ldist, ((size_t)nparts + 1) * kMaxLayers, err)) return false;
+    if (!h_dist) HIPCHECK(hipHostMalloc((void **)&h_dist, kMaxLayers * sizeof(double), hipHostMallocDefault));
+    DistArgs da;
+    da.nblocks = nb;
+    da.layers = plan.rc.layers;
+    da.lossless = plan.rc.rate_bpp <= 0.0;
+    da.ngroups = plan.ngroups();
+    da.nparts = nparts;
+    da.grp_b0 = (const int32_t *)grptab.ptr;
+    da.nhull = (const uint8_t *)nhull.ptr;
+    da.npasses = (const uint8_t *)npasses.ptr;
+    da.hkey = (const uint64_t *)hkey.ptr;
+    da.K = (const uint64_t *)thr.ptr;
+    da.dists = (const int64_t *)dists.ptr;
+    da.hdist = (const int64_t *)hdist.ptr;
+    da.weight = (const double *)weight.ptr;
+    da.part = (double *)ldist.ptr;
+    da.out = (double *)ldist.ptr + (size_t)nparts * kMaxLayers;
+    hipLaunchKernelGGL(k_layer_dist, dim3(nparts), dim3(kDistThreads), 0, stream, da);
+    hipLaunchKernelGGL(k_layer_dist_sum, dim3(1), dim3(64), 0, stream, da);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(h_dist, da.out, kMaxLayers * sizeof(double), hipMemcpyDeviceToHost, stream));
+    if (!host_wait(err)) return false;
+    std::memcpy(d, h_dist, kMaxLayers * sizeof(double));
+    return true;
 }
 
 // per-block layer tables for the thresholds in `thr` (kEvSelectBegin already recorded)

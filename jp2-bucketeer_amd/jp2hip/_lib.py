@@ -7,6 +7,7 @@ if the library or a gfx950 device is missing, calls raise ``Jp2hipError``.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from ctypes import (CFUNCTYPE, POINTER, Structure, byref, c_char_p, c_double, c_int, c_int32,
                     c_int64, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p)
@@ -125,6 +126,21 @@ class Stats(Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LayerReport(Structure):
+    """struct jp2hip_layer_report: per layer the threshold it was cut at,
+    the code-stream bytes through it and (when enabled, else NaN) the
+    predicted squared error left after it, summed over the image."""
+    _fields_ = [("layers", c_int32), ("distortion_valid", c_int32), ("threshold", c_double * 32),
+                ("bytes", c_int64 * 32), ("distortion", c_double * 32)]
+
+    def psnr(self, l: int, width: int, height: int, components: int, bits: int) -> float:
+        """The PSNR (dB) layer ``l``'s predicted distortion amounts to on a
+        width x height image of ``components`` ``bits``-bit samples."""
+        mse = self.distortion[l] / (width * height * components)
+        peak = float((1 << bits) - 1)
+        return math.inf if mse <= 0.0 else 10.0 * math.log10(peak * peak / mse)
+
+
 # every symbol include/jp2hip.h declares
 EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device_count", "jp2hip_device_ordinals",
            "jp2hip_recipe_init",
@@ -142,8 +158,14 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            "jp2hip_set_organisation", "jp2hip_batch_set_organisation", "jp2hip_tlm_segments",
            # tile-part divisions L and C (api.cpp, batch.cpp; jp2hip_tile_parts host only)
            "jp2hip_set_tile_part_divisions", "jp2hip_batch_set_tile_part_divisions", "jp2hip_tile_parts",
+           # fixed-slope layers and the per-layer report (api.cpp, batch.cpp; the check host only)
+           "jp2hip_set_layer_slopes", "jp2hip_batch_set_layer_slopes", "jp2hip_check_layer_slopes",
+           "jp2hip_set_layer_report", "jp2hip_layer_report",
            # device-memory policy (api.cpp; csrc/context.h EncodeEnd)
            "jp2hip_device_bytes", "jp2hip_set_memory_limits", "jp2hip_device_memory", "jp2hip_dma_engines")
+# ... but for the two whose names hold a digit, which the header scan of tests/test_abi.py does not read
+# (host only; bound in lib() like the rest, tests/test_slopes.py calls them)
+EXPORTS_WITH_DIGITS = ("jp2hip_slope_from_log2", "jp2hip_slope_to_log2")
 
 
 # int (*)(void *user, int64_t *values, int32_t n): in-place sum over ranks, 0 ok
@@ -213,6 +235,15 @@ def lib():
     L.jp2hip_tile_parts.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(Recipe), c_int32, c_int32,
                                     POINTER(c_uint32), c_int64]
     L.jp2hip_tile_parts.restype = c_int64
+    L.jp2hip_set_layer_slopes.argtypes = [c_void_p, POINTER(c_double), c_int32]
+    L.jp2hip_batch_set_layer_slopes.argtypes = [c_void_p, POINTER(c_double), c_int32]
+    L.jp2hip_check_layer_slopes.argtypes = [POINTER(c_double), c_int32, POINTER(Recipe)]
+    L.jp2hip_slope_from_log2.argtypes = [c_double, c_int32]
+    L.jp2hip_slope_from_log2.restype = c_double
+    L.jp2hip_slope_to_log2.argtypes = [c_double, c_int32]
+    L.jp2hip_slope_to_log2.restype = c_double
+    L.jp2hip_set_layer_report.argtypes = [c_void_p, c_int32]
+    L.jp2hip_layer_report.argtypes = [c_void_p, POINTER(LayerReport)]
     L.jp2hip_device_bytes.argtypes = [c_void_p]
     L.jp2hip_device_bytes.restype = c_int64
     L.jp2hip_set_memory_limits.argtypes = [c_void_p, c_int64, c_int64]
@@ -347,6 +378,31 @@ def tile_parts(width: int, height: int, components: int, bits: int, rcp: Recipe,
     if int(lib().jp2hip_tile_parts(width, height, components, bits, byref(rcp), bits_, tile, buf, n)) != n:
         raise Jp2hipError(last_error())
     return list(buf[:n])
+
+
+def slopes_array(slopes):
+    """(ctypes double array or None, n) of a sequence of layer thresholds."""
+    s = [float(x) for x in slopes] if slopes is not None else []
+    return ((c_double * len(s))(*s) if s else None), len(s)
+
+
+def check_layer_slopes(slopes, rcp: Recipe | None = None) -> None:
+    """jp2hip_check_layer_slopes (no GPU): raises Jp2hipError, naming the
+    entry, for thresholds jp2hip_set_layer_slopes -- or, with ``rcp``, an
+    encode of that recipe -- refuses."""
+    arr, n = slopes_array(slopes)
+    if lib().jp2hip_check_layer_slopes(arr, n, byref(rcp) if rcp is not None else None) != 0:
+        raise Jp2hipError(last_error())
+
+
+def slope_from_log2(v: float, bits: int) -> float:
+    """The threshold Kdu-Layer-Info prints as ``v`` for ``bits``-bit samples: 2^(v + 2 bits)."""
+    return float(lib().jp2hip_slope_from_log2(v, bits))
+
+
+def slope_to_log2(s: float, bits: int) -> float:
+    """What Kdu-Layer-Info prints (before rounding) for threshold ``s``."""
+    return float(lib().jp2hip_slope_to_log2(s, bits))
 
 
 def tlm_segments(tiles, lengths) -> bytes:
@@ -510,6 +566,28 @@ class Encoder:
         ``Recipe.tparts_r``.  Not while the context is encoding."""
         if lib().jp2hip_set_tile_part_divisions(self._h, tparts_letters(letters)) != 0:
             raise Jp2hipError(last_error())
+
+    def set_layer_slopes(self, slopes=None):
+        """jp2hip_set_layer_slopes, for every later encode on this context and
+        its tile-split peers: one threshold per layer, layer 0 first, none
+        increasing (the last 0 for a lossless recipe); None or () turns the
+        fixed slopes off.  Not while the context is encoding."""
+        arr, n = slopes_array(slopes)
+        if lib().jp2hip_set_layer_slopes(self._h, arr, n) != 0:
+            raise Jp2hipError(last_error())
+
+    def set_layer_report(self, on: bool | int = True):
+        """jp2hip_set_layer_report: later encodes also sum the distortion
+        every layer leaves (one small kernel pair and a host wait more)."""
+        if lib().jp2hip_set_layer_report(self._h, int(on)) != 0:
+            raise Jp2hipError(last_error())
+
+    def layer_report(self) -> LayerReport:
+        """jp2hip_layer_report: the last successful encode's layers."""
+        r = LayerReport()
+        if lib().jp2hip_layer_report(self._h, byref(r)) != 0:
+            raise Jp2hipError(last_error())
+        return r
 
     def _take(self, out, n, copy=True):
         if not copy:

@@ -106,6 +106,10 @@ class GpuConverter(Converter):
     jp2hip_encode_file (jp2hip_split_peers), a smaller one takes a pool
     context.  ``tlm=True`` is Kakadu's ``ORGgen_tlm=yes``: every file gets
     TLM marker segments (Encoder.set_organisation on every context).
+    ``layer_slopes=[s0, s1, ...]`` is Kakadu's ``-slope``: every file's quality
+    layers are cut at these thresholds instead of by rate or by fraction
+    (Encoder.set_layer_slopes on every context; one per layer of the recipe,
+    the last 0 for lossless conversions).
 
     Safe for concurrent callers (the reference runs one ImageWorkerVerticle
     thread, MainVerticle.java:229-231; raising that count gives each call its
@@ -117,7 +121,8 @@ class GpuConverter(Converter):
     SPLIT_MIN_PIXELS = 256_000_000
 
     def __init__(self, devices: list[int] | None = None, host_threads: int = 0, per_gpu: int | None = None,
-                 split_devices: list[int] | None = None, split_min_pixels: int | None = None, tlm: bool = False):
+                 split_devices: list[int] | None = None, split_min_pixels: int | None = None, tlm: bool = False,
+                 layer_slopes=None):
         self.tmp_dir = Path(tempfile.gettempdir()) / self.WORKING_DIR_NAME
         self._pool, self._free = [], []
         self._cv = threading.Condition()
@@ -144,6 +149,8 @@ class GpuConverter(Converter):
                 self._split = _lib.Encoder(split_devices[0], host_threads)
                 if tlm:  # before the peers: they inherit it
                     self._split.set_organisation(tlm=True)
+                if layer_slopes is not None:
+                    self._split.set_layer_slopes(layer_slopes)
                 self._split.split_peers(list(split_devices[1:]), split_min_pixels)
                 self.split_world = len(split_devices)
         except _lib.Jp2hipError as e:
@@ -156,6 +163,14 @@ class GpuConverter(Converter):
         if tlm:  # ORGgen_tlm: TLM marker segments in every file this converter writes
             for e in self._pool:
                 e.set_organisation(tlm=True)
+        self.layer_slopes = None if layer_slopes is None else [float(x) for x in layer_slopes]
+        if layer_slopes is not None:
+            try:
+                for e in self._pool:
+                    e.set_layer_slopes(layer_slopes)
+            except _lib.Jp2hipError as e:
+                self.close()
+                raise IOError(BUCKETEER_001.format(f"(GPU converter init: {e})")) from e
         self._free = list(self._pool)
         # the slow configurations the library can see (queues, SDMA): logged once
         self.env_advice = _lib.env_check()
@@ -174,6 +189,7 @@ class GpuConverter(Converter):
         c._split, c._split_lock, c.split_world = None, threading.Lock(), 1
         c._closed = False
         c.tlm = False
+        c.layer_slopes = None
         c.unavailable = reason
         return c
 

@@ -219,8 +219,10 @@ def encode_split(encoder, d_ptr: int, nbytes: int, layout: Layout, conversion: i
     in the recipe and in the organisation: every rank's encoder has had the
     same ``set_organisation`` (with ``tlm`` the ranks sum their tile-part
     lengths through ``group`` and rank 0 writes the TLM marker segments;
-    ``file_len`` and the later ranks' offsets count them) and the same
-    ``set_tile_part_divisions``."""
+    ``file_len`` and the later ranks' offsets count them), the same
+    ``set_tile_part_divisions``, the same ``set_layer_slopes`` (no threshold
+    is exchanged then) and the same ``set_layer_report`` (the ranks' distortion
+    sums travel through ``group``; rank 0's ``layer_report()`` is the image's)."""
     sp = (group or SingleGroup()).split()
     return encoder.encode_device_split(d_ptr, nbytes, layout, conversion, sp, rcp)
 
