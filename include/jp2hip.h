@@ -375,6 +375,66 @@ int jp2hip_set_layer_slopes(jp2hip_ctx *ctx, const double *slopes, int32_t n);
  * that names the entry. */
 int jp2hip_check_layer_slopes(const double *slopes, int32_t n, const jp2hip_recipe *recipe);
 
+/* Explicit per-layer rates (Kakadu's -rate r1,r2,..., which lists the highest
+ * rate first; here layer 0 comes first): with n = recipe.layers rates set,
+ * rates_bpp[l] bounds the code-stream through layer l -- main header, TLM and
+ * tile-part headers included, as the single rate bounds the file's -- at
+ * floor(rates_bpp[l] * width * height / 8) bytes.  The rate loop steers every
+ * layer, not the last one: each has a byte budget of its own, lowered while
+ * the layer is over its target (DESIGN.md 4 states the rule; budgets only ever
+ * fall, so a layer may end below its target).  NULL / n = 0 turns it off.
+ *   - recipe.rate_bpp is no target.  > 0 only selects the irreversible recipe's
+ *     meaning of "not lossless", and every rate must be > 0.  With rate_bpp <= 0
+ *     the last layer takes every coded pass and its rate must be 0: Kakadu's
+ *     "-rate -,r2,...", a lossless file whose lower layers have named sizes.
+ *   - recipe.slope_skip is honoured as for a single rate, against the top
+ *     layer's target; with a lossless top layer it is off.
+ *   - stats.rate_iterations counts the loop's iterations (at most 8).  With
+ *     one layer the encode is the one recipe.rate_bpp = rates_bpp[0] gives.
+ *   - A lossless recipe's plan has one rate-control group while rates are set
+ *     (a byte target is the whole image's), not a group per -flush_period
+ *     stripe; the plan cache's key holds that, not the rates.
+ *   - Rates and fixed-slope layers exclude each other: setting one while the
+ *     other is set is refused.
+ *   - Collective like the slopes: peers of jp2hip_split_peers get the rates
+ *     here and inherit them when added later; over a caller's callback every
+ *     rank sets the same rates.
+ * Refused, with a message that names the entry (or the other setter): a NaN,
+ * an infinity, a negative value, a sequence that decreases anywhere (a last 0
+ * is the lossless top layer, no decrease), n outside 0..32; at the encode, n
+ * other than the recipe's layers, with rate_bpp <= 0 a last entry other than
+ * 0, with rate_bpp > 0 an entry of 0 (the context stays usable).  Not to be
+ * called while ctx is encoding. */
+int jp2hip_set_layer_rates(jp2hip_ctx *ctx, const double *rates_bpp, int32_t n);
+
+/* Host-only: the checks above on their own -- those of the encode too when
+ * `recipe` is given.  Returns 0, or < 0 with a message that names the entry. */
+int jp2hip_check_layer_rates(const double *rates_bpp, int32_t n, const jp2hip_recipe *recipe);
+
+/* Host-only, exported for tests: one step of the loop above, the text the
+ * device and the tile-split's host loop run, after iteration `it` (0..7) sized
+ * the code-stream.  The code-stream through layer l is fixed + part_bytes less
+ * layer_bytes[m] of the layers m > l; targets[l] < 0: the layer has no target
+ * (a lossless top layer, whose budget INT64_MAX stays).  Returns 1: halt (every
+ * targeted layer fits, or it = 7), budgets untouched; 0: the budgets of the
+ * layers that are over are lowered by (over << it) + (over >> 4) + 64, floored
+ * at 0, and clamped so that they never decrease with l; < 0: a bad argument. */
+int jp2hip_layer_rate_step(int32_t layers, int32_t it, int64_t fixed, int64_t part_bytes,
+                           const int64_t *layer_bytes, const int64_t *targets, int64_t *budgets);
+
+/* Host-only, exported for tests: what an encode of this image by these rates
+ * starts from -- targets[l] = max(0, floor(rate * W * H / 8) - T - E) and the
+ * first budgets max(0, targets[l] - (16 * tile-parts + 256 + 16 * (packets /
+ * layers) * (l + 1))) -- with tlm = 1 / `letters` as jp2hip_set_organisation /
+ * jp2hip_set_tile_part_divisions would set them.  A lossless top layer has
+ * target -1 and budget INT64_MAX.  info (may be NULL): T, E, the plan's
+ * tile-part count and packet count of the header estimate.  < 0 with a
+ * message for rates or a recipe the encodes refuse. */
+int jp2hip_layer_rate_targets(int32_t width, int32_t height, int32_t components, int32_t bits,
+                              const jp2hip_recipe *recipe, int32_t letters, int32_t tlm,
+                              const double *rates_bpp, int32_t n, int64_t *targets, int64_t *budgets,
+                              int64_t *info);
+
 /* Kdu-Layer-Info's number <-> a threshold for `bits`-bit samples:
  * s = 2^(v + 2 * bits). */
 double jp2hip_slope_from_log2(double v, int32_t bits);
@@ -638,6 +698,9 @@ int jp2hip_batch_set_tile_part_divisions(jp2hip_batch *b, int32_t letters);
 /* jp2hip_set_layer_slopes on every context of the queue; before the first
  * submit (< 0 after it, or for refused slopes). */
 int jp2hip_batch_set_layer_slopes(jp2hip_batch *b, const double *slopes, int32_t n);
+/* jp2hip_set_layer_rates on every context of the queue; before the first
+ * submit (< 0 after it, or for refused rates). */
+int jp2hip_batch_set_layer_rates(jp2hip_batch *b, const double *rates_bpp, int32_t n);
 /* Queue one image: convert `tiff_path` into `jpx_path` (written atomically)
  * with `conversion` (recipe NULL -> Bucketeer recipe), then upload it under
  * `image_id`.  Never blocks on the GPU; returns < 0 after close. */

@@ -298,9 +298,63 @@ int jp2hip_set_layer_slopes(jp2hip_ctx *ctx, const double *slopes, int32_t n) {
     if (jp2hip_check_layer_slopes(slopes, n, nullptr) != 0) return -1;
     if (!ctx) return fail("null context");
     std::lock_guard<std::mutex> lk(ctx->mu);
+    if (n && !ctx->rates.empty())
+        return fail("layer slopes: per-layer rates are set on this context (jp2hip_set_layer_rates); turn them off first");
     ctx->slopes.assign(slopes, slopes + n);
     for (jp2hip_ctx *p : ctx->peers)
         if (jp2hip_set_layer_slopes(p, slopes, n) != 0) return -1;
+    return 0;
+}
+
+int jp2hip_check_layer_rates(const double *rates_bpp, int32_t n, const jp2hip_recipe *recipe) {
+    std::string err;
+    return jp2hip::check_layer_rates(rates_bpp, n, recipe, err) ? 0 : fail(err);
+}
+
+int jp2hip_set_layer_rates(jp2hip_ctx *ctx, const double *rates_bpp, int32_t n) {
+    if (!rates_bpp) n = 0;
+    if (jp2hip_check_layer_rates(rates_bpp, n, nullptr) != 0) return -1;
+    if (!ctx) return fail("null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (n && !ctx->slopes.empty())
+        return fail("layer rates: fixed-slope layers are set on this context (jp2hip_set_layer_slopes); turn them off first");
+    ctx->rates.assign(rates_bpp, rates_bpp + n);
+    for (jp2hip_ctx *p : ctx->peers)
+        if (jp2hip_set_layer_rates(p, rates_bpp, n) != 0) return -1;
+    return 0;
+}
+
+int jp2hip_layer_rate_step(int32_t layers, int32_t it, int64_t fixed, int64_t part_bytes, const int64_t *layer_bytes,
+                           const int64_t *targets, int64_t *budgets) {
+    if (layers < 1 || layers > jp2hip::kMaxLayers || it < 0 || it > 7 || !layer_bytes || !targets || !budgets)
+        return fail("layer rate step: layers outside 1 .. 32, it outside 0 .. 7, or a null array");
+    return jp2hip::layer_rate_step(layers, it, fixed, part_bytes, layer_bytes, targets, budgets);
+}
+
+int jp2hip_layer_rate_targets(int32_t width, int32_t height, int32_t components, int32_t bits,
+                              const jp2hip_recipe *recipe, int32_t letters, int32_t tlm, const double *rates_bpp,
+                              int32_t n, int64_t *targets, int64_t *budgets, int64_t *info) {
+    if (!recipe || !rates_bpp || !targets || !budgets) return fail("null argument");
+    jp2hip::Plan plan;
+    std::string err;
+    jp2hip_recipe rc = *recipe;
+    if (!jp2hip::check_layer_rates(rates_bpp, n, &rc, err) || !letters_ok(letters, err) ||
+        !jp2hip::resolve_tiles(rc, width, height, err) ||
+        !jp2hip::build_plan(plan, rc, width, height, components, bits, err, rc.rate_bpp <= 0.0))
+        return fail(err);
+    if (n != rc.layers) return fail("layer rates: none given");
+    std::vector<int> count;
+    if (!jp2hip::tile_part_counts(plan, letters, count, err)) return fail(err);
+    int64_t ntp = 0;
+    for (int c : count) ntp += c;
+    const int64_t T = tlm ? jp2hip::tlm_bytes(ntp) : 0, E = jp2hip::tile_part_division_bytes(plan, letters, ntp);
+    jp2hip::layer_rate_targets(plan, rates_bpp, n, T + E, targets, budgets);
+    if (info) {
+        info[0] = T;
+        info[1] = E;
+        info[2] = plan.ntileparts;
+        info[3] = plan.npackets;
+    }
     return 0;
 }
 
@@ -535,7 +589,8 @@ int jp2hip_split_peers(jp2hip_ctx *ctx, const int32_t *ordinals, int32_t n, int6
         }
         p->org = ctx->org;  // (jp2hip_set_organisation: peers added later inherit it)
         p->tparts = ctx->tparts;  // (jp2hip_set_tile_part_divisions likewise)
-        p->slopes = ctx->slopes;  // (jp2hip_set_layer_slopes, jp2hip_set_layer_report likewise)
+        p->slopes = ctx->slopes;  // (jp2hip_set_layer_slopes, _rates, jp2hip_set_layer_report likewise)
+        p->rates = ctx->rates;
         p->report_on = ctx->report_on;
         made.push_back(p);
     }

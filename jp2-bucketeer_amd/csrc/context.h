@@ -19,6 +19,9 @@ struct PlanCache {
     bool valid = false;
     jp2hip_recipe rc;
     int w = 0, h = 0, nc = 0, bits = 0;
+    // part of the key: a lossless recipe encoded by per-layer rates has one
+    // rate-control group, not the flush stripes (Plan::one_group)
+    bool one_group = false;
     jp2hip::Plan plan;
     // the tables are the plan's cut by the context's tile-part divisions
     // (tabs.letters; tabs_ok false: none built for this plan yet), which are
@@ -50,6 +53,11 @@ struct jp2hip_ctx {
     // every encode, no part of the plan cache's key; jp2hip_set_layer_report
     // and what the last successful encode's layers came to
     std::vector<double> slopes;
+    // jp2hip_set_layer_rates: the bound (bpp) on the code-stream through each
+    // layer (empty: off; excludes slopes), read by every encode.  The rates
+    // are no part of the plan cache's key; that they are set is, for a
+    // lossless recipe (PlanCache::one_group)
+    std::vector<double> rates;
     int32_t report_on = 0;
     bool report_set = false;
     struct jp2hip_layer_report report{};

@@ -228,6 +228,30 @@ __device__ __forceinline__ void rate_step(RateState *rs, const T2Summary *sum, i
     *out_rs = r;
     *out_sum = *sum;
 }
+// The same step for an encode by per-layer rates (jp2hip_set_layer_rates):
+// every layer has a target and a budget of its own in device memory (target:
+// kMaxLayers values, < 0 = none; budget: the buffer k_select reads), and
+// layer_rate_step (jp2hip_internal.h, shared with the host) decides.
+// r.budget and r.target are not used; with one layer the two steps agree.
+__device__ __forceinline__ void rate_step_layers(RateState *rs, const T2Summary *sum, int L, const int64_t *target,
+                                                 int64_t *budget, RateState *out_rs, T2Summary *out_sum) {
+    RateState r = *rs;
+    if (r.halt) return;
+    if (sum->err) {
+        r.halt = 1;
+    } else if (r.it == 0 && r.skip_target > 0 && sum->skipped && sum->t1_bytes < r.skip_target) {
+        r.safety = 1;
+        r.halt = 1;
+    } else {
+        r.iters++;
+        r.cs_bytes = r.fixed + sum->part_bytes;
+        if (layer_rate_step(L, r.it, r.fixed, sum->part_bytes, sum->layer_bytes, target, budget)) r.halt = 1;
+        else r.it++;
+    }
+    *rs = r;
+    *out_rs = r;
+    *out_sum = *sum;
+}
 
 // Files each block's coded planes in k_t1_cm3's per-depth work lists
 // (T1ItemArgs, gpu_encoder.h); called by every thread of a thread-per-block

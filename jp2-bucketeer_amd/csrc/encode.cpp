@@ -9,6 +9,9 @@
 // sized for the worst case (pool_worst: ranks cannot repeat an exchange).
 // With fixed-slope layers (jp2hip_set_layer_slopes) neither runs: both encodes
 // apply the caller's thresholds where the lossless encode applies its own.
+// With per-layer rates (jp2hip_set_layer_rates) both loops run with a target
+// and a budget per layer and one step, layer_rate_step (jp2hip_internal.h),
+// also for a lossless recipe, whose plan then has one rate-control group.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -89,6 +92,42 @@ bool check_layer_slopes(const double *s, int n, const jp2hip_recipe *rc, std::st
     return true;
 }
 
+bool check_layer_rates(const double *r, int n, const jp2hip_recipe *rc, std::string &err) {
+    if (n < 0 || n > kMaxLayers || (n > 0 && !r)) {
+        err = "layer rates: n = " + std::to_string(n) + " is outside 0 .. " + std::to_string(kMaxLayers) +
+              " (or no rates were given)";
+        return false;
+    }
+    for (int i = 0; i < n; i++) {
+        const std::string at = "layer rates: rates[" + std::to_string(i) + "]";
+        if (std::isnan(r[i])) err = at + " is NaN";
+        else if (std::isinf(r[i])) err = at + " is infinite";
+        else if (std::signbit(r[i])) err = at + " = " + std::to_string(r[i]) + " is negative";
+        else if (i && r[i] < r[i - 1] && !(i == n - 1 && r[i] == 0.0))
+            err = at + " decreases from rates[" + std::to_string(i - 1) + "]: the rates rise from layer 0 on";
+        else continue;
+        return false;
+    }
+    if (!rc || !n) return true;
+    if (n != rc->layers) {
+        err = "layer rates: n = " + std::to_string(n) + " rates for an encode of recipe.layers = " +
+              std::to_string(rc->layers);
+        return false;
+    }
+    if (rc->rate_bpp <= 0.0 && r[n - 1] != 0.0) {
+        err = "layer rates: rates[" + std::to_string(n - 1) + "], the last, must be 0 with rate_bpp <= 0 " +
+              "(the last layer takes every coded pass)";
+        return false;
+    }
+    for (int i = 0; i < n && rc->rate_bpp > 0.0; i++)
+        if (r[i] == 0.0) {
+            err = "layer rates: rates[" + std::to_string(i) + "] is 0 with rate_bpp > 0 (0 names a lossless top layer: " +
+                  "rate_bpp <= 0)";
+            return false;
+        }
+    return true;
+}
+
 namespace {
 
 // The slope keys of a context's thresholds: the doubles' bit patterns.
@@ -135,6 +174,8 @@ int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conv
     // fixed-slope layers: the thresholds against this encode's recipe (refused
     // before the encode begins: the context stays as it was)
     if (!check_layer_slopes(ctx->slopes.data(), (int)ctx->slopes.size(), &rc, terr)) return fail(terr);
+    // per-layer rates likewise
+    if (!check_layer_rates(ctx->rates.data(), (int)ctx->rates.size(), &rc, terr)) return fail(terr);
     meta = source_meta(*lay);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
     ctx->gpu.take_waits();     // count this encode's host waits (stats)
     ctx->gpu.begin_encode();
@@ -263,13 +304,20 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     if (!unit_grid(*lay, grid, err) || !prepare_source(ctx, grid, d_src, src_len, lay, 0, lay->height, ulay, uoffs, err))
         return fail(err);
     PlanCache &pc = ctx->pc;
+    // per-layer rates (jp2hip_set_layer_rates): byte targets for the whole
+    // image, so a lossless recipe's plan has one rate-control group, not the
+    // flush stripes -- part of the cache's key (the rates themselves are not)
+    const bool by_rates = !ctx->rates.empty();
+    const bool one_group = by_rates && rc.rate_bpp <= 0.0;
     if (!pc.valid || pc.w != lay->width || pc.h != lay->height || pc.nc != lay->components || pc.bits != lay->bits ||
-        std::memcmp(&pc.rc, &rc, sizeof rc) != 0) {
+        pc.one_group != one_group || std::memcmp(&pc.rc, &rc, sizeof rc) != 0) {
         pc.valid = false;
         pc.tabs_ok = false;
-        if (!build_plan(pc.plan, rc, lay->width, lay->height, lay->components, lay->bits, err)) return fail(err);
+        if (!build_plan(pc.plan, rc, lay->width, lay->height, lay->components, lay->bits, err, one_group))
+            return fail(err);
         main_header(pc.plan, pc.mh0, nullptr, nullptr);
         pc.rc = rc;
+        pc.one_group = one_group;
         pc.w = lay->width; pc.h = lay->height; pc.nc = lay->components; pc.bits = lay->bits;
         pc.valid = true;
     } else {
@@ -282,9 +330,8 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         pc.tabs_ok = false;
         t2_tables(plan, 0, plan.ntx * plan.nty, 0, pc.tabs, ctx->tparts);
         if (!tile_parts_fit(plan, pc.tabs, err)) return fail(err);
-        // E (rate-driven encodes only; a lossless one never sees it)
-        pc.division_bytes =
-            rc.rate_bpp > 0.0 ? tile_part_division_bytes(plan, ctx->tparts, (int64_t)pc.tabs.tp.size()) : 0;
+        // E (read by encodes with a target only: a lossless one without rates never sees it)
+        pc.division_bytes = tile_part_division_bytes(plan, ctx->tparts, (int64_t)pc.tabs.tp.size());
         pc.tabs_ok = true;
     }
     const bool prof = ctx->cfg.profile != 0;
@@ -293,12 +340,22 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     const int64_t tlm = ctx->org.tlm ? tlm_bytes((int64_t)pc.tabs.tp.size()) : 0;
     if (ctx->org.tlm && (int64_t)pc.tabs.tp.size() > kTlmMaxEntries)
         return fail("tlm: more tile-parts than 256 TLM marker segments hold");
-    const int64_t E = pc.division_bytes;  // what the L / C divisions add
+    // what the L / C divisions add (counted by encodes with a target)
+    const int64_t E = rc.rate_bpp > 0.0 || by_rates ? pc.division_bytes : 0;
     // fixed-slope layers (jp2hip_set_layer_slopes): no target, so nothing is
     // predicted and every plane is coded
     const bool fixed = !ctx->slopes.empty();
     const std::vector<uint64_t> keys = slope_keys(ctx->slopes);
     int64_t skip_target = fixed ? -1 : skip_target_of(rc, plan.w, plan.h, tlm + E);
+    // per-layer rates: every layer's target and first budget;
+    // slope prediction aims at the top layer's target, the largest (a
+    // lossless top layer: off)
+    int64_t ltarget[kMaxLayers] = {}, lbudget[kMaxLayers] = {};
+    if (by_rates) {
+        layer_rate_targets(plan, ctx->rates.data(), rc.layers, tlm + E, ltarget, lbudget);
+        skip_target = rc.slope_skip && rc.rate_bpp > 0.0 ? ltarget[rc.layers - 1] : -1;
+        if (!ctx->gpu.rates_load(ltarget, lbudget, err)) return fail(err);
+    }
     // tier-2 tables first: every host->device copy of the encode is issued
     // while the stream is idle (a copy queued behind kernels holds up the
     // copy engine for the other contexts)
@@ -309,7 +366,7 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     std::memset(&sum, 0, sizeof sum);
     int iters = 0;
     int64_t cs_bytes = 0;
-    if (fixed || rc.rate_bpp <= 0.0) {
+    if (fixed || (rc.rate_bpp <= 0.0 && !by_rates)) {
         // lossless: per -flush_period stripe, layer l keeps the passes whose
         // slopes clear lossless_layer_frac(l) of the stripe's tier-1 bytes;
         // fixed slopes: layer l keeps the passes whose slopes clear the
@@ -337,8 +394,10 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         // heavier takes a second wait for its next iterations
         RateState init;
         std::memset(&init, 0, sizeof init);
-        init.target = rate_target_of(rc, plan.w, plan.h, tlm + E);
-        init.budget = first_budget_of(plan, init.target);
+        // (by rates: the device reads the layers' targets and budgets from
+        // what rates_load sent; these two fields are not used)
+        init.target = by_rates ? ltarget[rc.layers - 1] : rate_target_of(rc, plan.w, plan.h, tlm + E);
+        init.budget = by_rates ? lbudget[rc.layers - 1] : first_budget_of(plan, init.target);
         // the cs_bytes the loop compares leaves E out, as it leaves the TLM
         // out: the encode without letters, at the lower target
         init.fixed = (int64_t)mh_bytes + 2 - E;
@@ -346,7 +405,8 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
         RateState rs;
         bool restart = true;
         for (int grow = 0;;) {
-            if (!ctx->gpu.rate_loop(plan, init, restart, restart ? 1 : 2, prof, st, rs, sum, err)) return fail(err);
+            if (!ctx->gpu.rate_loop(plan, init, restart, restart ? 1 : 2, prof, st, rs, sum, err, by_rates))
+                return fail(err);
             restart = false;
             if ((sum.err & kErrSlotPool) && grow++ < 2) {
                 // the decision-stream pool was short: again with the size
@@ -425,7 +485,11 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     if (!unit_grid(*lay, grid, err)) return fail(err);
     int enc_nc, enc_bits;  // the plan sees what the code-stream carries
     encoded_format(*lay, enc_nc, enc_bits);
-    if (!build_plan(full, rc, lay->width, lay->height, enc_nc, enc_bits, err)) return fail(err);
+    // per-layer rates (collective, like the slopes): a lossless recipe's plan
+    // then has one rate-control group, and takes the rate-driven exchange
+    const bool by_rates = !ctx->rates.empty();
+    if (!build_plan(full, rc, lay->width, lay->height, enc_nc, enc_bits, err, by_rates && rc.rate_bpp <= 0.0))
+        return fail(err);
     int tr0, tr1;
     if (untiled(recipe)) {  // one tile row, all of it rank 0's (jp2hip_split_rows with tile_h = 0)
         tr0 = rank ? 1 : 0;
@@ -463,8 +527,9 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     const int64_t ntp_full = ctx->org.tlm ? ntp[(size_t)ntiles] : 0;
     if (ntp_full > kTlmMaxEntries) return fail("tlm: more tile-parts than 256 TLM marker segments hold");
     const int64_t tlm = tlm_bytes(ntp_full);
-    // E: what the L / C divisions add (rate-driven encodes only)
-    const int64_t E = rc.rate_bpp > 0.0 ? tile_part_division_bytes(full, letters, ntp[(size_t)ntiles]) : 0;
+    // E: what the L / C divisions add (encodes with a target only)
+    const int64_t E =
+        rc.rate_bpp > 0.0 || by_rates ? tile_part_division_bytes(full, letters, ntp[(size_t)ntiles]) : 0;
     // slope prediction over the whole image: the plane histogram is summed
     // over ranks (one all-reduce of kSlopeBins + 1 int64, the last a failure
     // flag, so a rank that failed earlier still joins the exchange)
@@ -472,6 +537,11 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // nothing predicted, no threshold exchange
     const bool fixed = !ctx->slopes.empty();
     int64_t skip_target = fixed ? -1 : skip_target_of(rc, full.w, full.h, tlm + E);
+    int64_t ltarget[kMaxLayers] = {}, lbudget[kMaxLayers] = {};
+    if (by_rates) {  // (as encode_core)
+        layer_rate_targets(full, ctx->rates.data(), rc.layers, tlm + E, ltarget, lbudget);
+        skip_target = rc.slope_skip && rc.rate_bpp > 0.0 ? ltarget[rc.layers - 1] : -1;
+    }
     bool hist_done = false;
     GpuEncoder::HistReduce reduce = [&](std::vector<int64_t> &h) {
         hist_done = true;
@@ -500,7 +570,8 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     int64_t cs_bytes = 0;
     T2Summary sum;
     std::memset(&sum, 0, sizeof sum);
-    int64_t g_tp_hdr = 0;                          // whole-image sums of the last pass
+    int64_t g_part = 0;                            // whole-image sums of the last pass: tile-part bytes,
+    int64_t g_tp_hdr = 0;                          // tile-part header bytes and packet bytes per layer
     std::vector<int64_t> g_layer((size_t)L, 0);    // (Kdu-Layer-Info)
     std::vector<uint8_t> mh;
     main_header(full, mh, nullptr, nullptr);
@@ -533,6 +604,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
             }
         }
         if (!exchange(v, 1, rok) || !rok) return false;
+        g_part = v[0];
         cs_bytes = (int64_t)mh.size() + 2 + v[0] - E;  // (without E, as the target: added back below)
         g_tp_hdr = v[2];
         g_layer.assign(v.begin() + 3, v.begin() + 3 + L);
@@ -557,7 +629,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
             skip_target = -1;
             iters = 0;
         }
-        if (rc.rate_bpp <= 0.0) {
+        if (rc.rate_bpp <= 0.0 && !by_rates) {
             // lossless: every -flush_period stripe's layers come from its own
             // tier-1 bytes (the plan's rate-control groups; a rank holds
             // whole stripes), so the selection needs no exchange -- only the
@@ -571,14 +643,23 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
         const int64_t target = rate_target_of(rc, full.w, full.h, tlm + E);  // (cs_bytes: without the TLM and E, as the target)
         int64_t budget = first_budget_of(full, target);
         bool rerun = false;
+        if (by_rates) budgets.assign(lbudget, lbudget + L);
         for (int it = 0; it < 8; it++) {
             if (budget < 0) budget = 0;
-            for (int l = 0; l < L; l++) budgets[l] = budget >> (L - 1 - l);
+            for (int l = 0; l < L && !by_rates; l++) budgets[l] = budget >> (L - 1 - l);
             if (!round(false)) return fail(err);
             if (it == 0 && skip_target > 0) {
                 int64_t v[2] = {have ? sum.t1_bytes : 0, have ? sum.skipped : 0};
                 if (!allreduce(v, 2)) return fail("split: all-reduce failed");
                 if (v[1] && v[0] < skip_target) { rerun = true; break; }
+            }
+            if (by_rates) {
+                // every layer against its own target: the device loop's step
+                // (layer_rate_step) on the whole image's sums
+                if (layer_rate_step(L, it, (int64_t)mh.size() + 2 - E, g_part, g_layer.data(), ltarget,
+                                    budgets.data()))
+                    break;
+                continue;
             }
             if (cs_bytes <= target) break;
             // exponential back-off + 1/16 of the overshoot + 64 B (device_common.h rate_step)

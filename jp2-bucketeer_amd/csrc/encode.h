@@ -27,6 +27,11 @@ jp2hip_recipe recipe_of(const jp2hip_recipe *recipe, int conversion);
 // that increases are refused; with rc (the encode's recipe) also n other than
 // rc->layers and, lossless, a last entry other than 0.  err names the entry.
 bool check_layer_slopes(const double *slopes, int n, const jp2hip_recipe *rc, std::string &err);
+// jp2hip_set_layer_rates' rates likewise: a NaN, an infinity, a negative value
+// and a sequence that decreases (a last 0 after positive rates is the lossless
+// top layer, no decrease) are refused; with rc also n other than rc->layers, a
+// last entry other than 0 under rate_bpp <= 0 and a 0 entry under rate_bpp > 0.
+bool check_layer_rates(const double *rates, int n, const jp2hip_recipe *rc, std::string &err);
 int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
                 const jp2hip_recipe *recipe, uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start,
                 double h2d_ms);

@@ -51,7 +51,9 @@ struct FrontJob;  // front.hip
     /* S1b sample expansion (expand.hip): the 8-bit copy, its unit offsets and the colour table */           \
     X(expanded) X(exoff) X(exlut)                                                                             \
     /* the layer report's per-workgroup distortion sums and their totals (k_layer_dist) */                   \
-    X(ldist)
+    X(ldist)                                                                                                  \
+    /* an encode by per-layer rates: kMaxLayers targets, then kMaxLayers first budgets (rates_load) */        \
+    X(ltarget)
 
 // Owns all device memory of a context; buffers only grow while the context
 // stays within its soft limit, so repeated encodes of the same geometry never
@@ -170,8 +172,15 @@ class GpuEncoder {
     // `batch` iterations enqueued per host wait; returns the final state and
     // the summary of the selection it stopped at.  restart = begin a new loop
     // (else continue the one on the device).
+    // by_rates: an encode by per-layer rates -- the targets and first budgets
+    // of rates_load steer every layer (rate_step_layers); init.budget and
+    // init.target are not used
     bool rate_loop(const Plan &plan, const RateState &init, bool restart, int batch, bool profile, StageTimes &st,
-                   RateState &rs, T2Summary &sum, std::string &err);
+                   RateState &rs, T2Summary &sum, std::string &err, bool by_rates = false);
+    // an encode by per-layer rates: its layers' targets and first budgets
+    // (kMaxLayers each; layer_rate_targets) into device memory through the
+    // pinned staging, issued with the tier-2 tables while the stream is idle
+    bool rates_load(const int64_t *target, const int64_t *first_budget, std::string &err);
     // the device code-stream buffer t2_emit writes, sized for part_bytes
     // (t2_emit reserves it too; the split path reserves before its exchange)
     bool t2_reserve(uint64_t part_bytes, std::string &err);
@@ -215,12 +224,13 @@ class GpuEncoder {
     bool hull_launch(const Plan &plan, std::string &err);
     bool front_dumps(const FrontJob &j, std::string &err);
     bool apply_thresholds(const Plan &plan, const int *halt, std::string &err);
-    void select_launch(const Plan &plan, const int *halt, const RateState *init = nullptr, RateState *rs = nullptr);
+    void select_launch(const Plan &plan, const int *halt, const RateState *init = nullptr, RateState *rs = nullptr,
+                       bool by_rates = false);
     T2Args t2_args(const Plan &plan) const;
     // tier-2 sizing; with rs (device rate loop) k_t2_total also runs the
     // loop's step, leaving state + summary at out_rs (host-mapped)
     void t2_size_launch(const Plan &plan, bool with_kc, const int *halt, RateState *rs = nullptr,
-                        RateState *out_rs = nullptr);
+                        RateState *out_rs = nullptr, bool by_rates = false);
     bool host_wait(std::string &err);
     // The code-stream D2H on an SDMA engine (ROCr hsa_amd_memory_async_copy):
     // the HIP runtime moves a device -> pinned-host copy with a blit kernel

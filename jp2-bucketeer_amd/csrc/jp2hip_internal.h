@@ -119,6 +119,9 @@ struct Plan {
     // bytes, oracle lossless_budget); rate-driven: the whole image, one group
     std::vector<int32_t> grp_b0;
     int ngroups() const { return (int)grp_b0.size() - 1; }
+    // one group whatever the recipe: a lossless recipe encoded by per-layer
+    // rates (jp2hip_set_layer_rates), whose byte targets are the whole image's
+    bool one_group = false;
     // identity of this plan's contents (build_plan / make_subplan): a device
     // context that already holds the tables of generation `gen` skips
     // uploading them again
@@ -126,7 +129,7 @@ struct Plan {
 };
 
 bool build_plan(Plan &plan, const jp2hip_recipe &rc, int w, int h, int nc, int bits,
-                std::string &err);
+                std::string &err, bool one_group = false);
 // The largest tile side: BlockDesc::x0 / y0 are 16 bits, and a
 // tile-component plane of at most 2^30 elements is indexed with an int.
 constexpr int kMaxTileSide = 32768;
@@ -282,6 +285,51 @@ struct RateState {
     int64_t budget, target, fixed, skip_target, cs_bytes;
     int32_t it, halt, safety, iters;
 };
+// Rate control by per-layer rates (jp2hip_set_layer_rates): one
+// step of the loop after iteration `it`'s tier-2 sizing pass, the text the
+// device (rate_step_layers, device_common.h), the tile-split's host loop and
+// jp2hip_layer_rate_step all run.  target[l] < 0: the layer has no target (a
+// lossless top layer; its budget is kRateNoBudget and stays).  The
+// code-stream through layer l is S[l] = fixed + part_bytes - sum over m > l
+// of layer_bytes[m].  Returns 1 (halt: every targeted layer fits, or it == 7;
+// the budgets stay), else 0 with the budgets of the layers that are over
+// lowered -- the single-rate step, per layer -- floored at 0 and clamped so
+// that they never decrease with l.
+#if defined(__HIP__) || defined(__HIPCC__)
+#define JP2HIP_RATE_HD __host__ __device__
+#else
+#define JP2HIP_RATE_HD
+#endif
+constexpr int64_t kRateNoBudget = INT64_MAX;
+JP2HIP_RATE_HD inline int layer_rate_step(int L, int it, int64_t fixed, int64_t part_bytes,
+                                          const int64_t *layer_bytes, const int64_t *target, int64_t *budget) {
+    bool fits = true;
+    int64_t S = fixed + part_bytes;
+    for (int l = L - 1; l >= 0; l--) {
+        if (target[l] >= 0 && S > target[l]) fits = false;
+        S -= layer_bytes[l];
+    }
+    if (fits || it >= 7) return 1;
+    S = fixed + part_bytes;
+    for (int l = L - 1; l >= 0; l--) {
+        if (target[l] >= 0 && S > target[l]) {
+            // exponential back-off + 1/16 of the overshoot + 64 B, as the oracle
+            const int64_t over = S - target[l];
+            budget[l] -= (over << it) + (over >> 4) + 64;
+            if (budget[l] < 0) budget[l] = 0;
+        }
+        S -= layer_bytes[l];
+    }
+    for (int l = L - 2; l >= 0; l--)
+        if (budget[l] > budget[l + 1]) budget[l] = budget[l + 1];
+    return 0;
+}
+// The targets and first budgets of `L` rates for a w x h image (P's tile-part
+// and packet counts are the header estimate's; org = T + E, what the TLM and
+// the tile-part divisions take from every layer); a last rate of 0 under
+// rate_bpp <= 0 is the lossless top layer: no target, kRateNoBudget.
+void layer_rate_targets(const Plan &P, const double *rates, int L, int64_t org, int64_t *target, int64_t *budget);
+
 // Main header (SOC .. COM) for the Kdu-Layer-Info values (nullptr: zeros;
 // the length does not depend on them).
 void main_header(const Plan &P, std::vector<uint8_t> &v, const uint64_t *K, const int64_t *layer_end);

@@ -222,7 +222,9 @@ struct SelectArgs {
     const int *halt;  // device rate loop: nothing to do once it has stopped
     // device rate loop, first iteration: the budgets come from `init` (every
     // workgroup derives them), and k_select's workgroup 0 writes the loop's
-    // state and budgets (what a separate init launch did)
+    // state and budgets (what a separate init launch did).  init_on = 2, an
+    // encode by per-layer rates: the first budgets are `budget`'s (device
+    // memory, one per layer), which workgroup 0 copies to budget_w for the step
     int init_on;
     RateState init;
     RateState *rs;
@@ -294,7 +296,7 @@ __device__ __forceinline__ void select_bins(const SelectArgs &a, SelBins &sh, in
     __syncthreads();
     if (tid < L) {
         // (a negative budget takes nothing, as 0 does: every segment has bytes)
-        const int64_t B = a.init_on    ? (a.init.budget < 0 ? 0 : a.init.budget) >> (L - 1 - tid)
+        const int64_t B = a.init_on == 1 ? (a.init.budget < 0 ? 0 : a.init.budget) >> (L - 1 - tid)
                           : a.lossless ? (int64_t)((a.gtot[g] * (unsigned long long)a.frac[tid]) >> 16)
                                        : a.budget[(size_t)g * kMaxLayers + tid];
         const int64_t T = B < 0 ? 0 : B;
@@ -359,7 +361,9 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
         r.cs_bytes = 0;
         if (r.budget < 0) r.budget = 0;
         *a.rs = r;
-        rate_budgets(r, a.layers, a.budget_w);
+        if (a.init_on == 1) rate_budgets(r, a.layers, a.budget_w);
+        else
+            for (int l = 0; l < a.layers; l++) a.budget_w[l] = a.budget[l];
     }
     if (gb0 + (int)blockIdx.x * kSelThreads >= gb1) return;  // (the whole workgroup)
     select_bins(a, sh, g);
@@ -807,7 +811,8 @@ bool GpuEncoder::hull_launch(const Plan &plan, std::string &err) {
 // k_select per rate-control group: lossless budgets from each group's tier-1
 // bytes, else from `budget` (the device rate loop's) -- thresholds of group g
 // -> thr[g * kMaxLayers ..), Kc -> thr[(G + g) * kMaxLayers ..)
-void GpuEncoder::select_launch(const Plan &plan, const int *halt, const RateState *init, RateState *rs) {
+void GpuEncoder::select_launch(const Plan &plan, const int *halt, const RateState *init, RateState *rs,
+                               bool by_rates) {
     const int nb = (int)plan.blocks.size(), G = plan.ngroups();
     if (!nb) return;
     SelectArgs sa;
@@ -829,11 +834,13 @@ void GpuEncoder::select_launch(const Plan &plan, const int *halt, const RateStat
     sa.Kc = (uint64_t *)thr.ptr + (size_t)G * kMaxLayers;
     sa.grp_b0 = (const int32_t *)grptab.ptr;
     sa.grp_seg0 = (const uint32_t *)grptab.ptr + G + 1;
-    sa.lossless = plan.rc.rate_bpp <= 0.0;
+    sa.lossless = plan.rc.rate_bpp <= 0.0 && !by_rates;  // (by rates: budgets, whatever the top layer is)
     sa.gtot = (const unsigned long long *)gtot.ptr;
     for (int l = 0; l < plan.rc.layers; l++) sa.frac[l] = lossless_layer_frac(l, plan.rc.layers);
-    sa.init_on = init != nullptr;
+    sa.init_on = init ? (by_rates ? 2 : 1) : 0;
     if (init) sa.init = *init;
+    // by rates, first iteration: the first budgets rates_load placed behind the targets
+    if (init && by_rates) sa.budget = (const int64_t *)ltarget.ptr + kMaxLayers;
     sa.rs = rs;
     sa.budget_w = (int64_t *)budget.ptr;
     sa.dbg = nullptr;
@@ -938,12 +945,22 @@ bool GpuEncoder::apply_thresholds(const Plan &plan, const int *halt, std::string
     return true;
 }
 
+// An encode by per-layer rates: kMaxLayers targets, then kMaxLayers first
+// budgets (layer_rate_targets), which the loop's first k_select and every step read
+bool GpuEncoder::rates_load(const int64_t *target, const int64_t *first_budget, std::string &err) {
+    HIPCHECK(hipSetDevice(device));
+    int64_t tb[2 * kMaxLayers];
+    std::memcpy(tb, target, sizeof(int64_t) * kMaxLayers);
+    std::memcpy(tb + kMaxLayers, first_budget, sizeof(int64_t) * kMaxLayers);
+    return ensure<int64_t>(ltarget, 2 * kMaxLayers, err) && h2d(ltarget.ptr, tb, sizeof tb, err);
+}
+
 // Device rate loop (RateState, jp2hip_internal.h): the first k_select of a
 // restart writes the initial state; the step itself is rate_step in
 // device_common.h, run by the sizing totals (t2_total_body: the last
 // workgroup of k_t2_wave<false>, or k_t2_total)
 bool GpuEncoder::rate_loop(const Plan &plan, const RateState &init, bool restart, int batch, bool profile,
-                           StageTimes &st, RateState &rs, T2Summary &sum, std::string &err) {
+                           StageTimes &st, RateState &rs, T2Summary &sum, std::string &err, bool by_rates) {
     HIPCHECK(hipSetDevice(device));
     if (!ensure<RateState>(rstate, 1, err)) return false;
     if (!h_rs) {  // host-mapped: k_rate_step writes the state and summary here
@@ -955,9 +972,9 @@ bool GpuEncoder::rate_loop(const Plan &plan, const RateState &init, bool restart
     HIPCHECK(hipEventRecord(ev[kEvSelectBegin], stream));
     for (int i = 0; i < batch; i++) {
         // (the first k_select of a restart also initialises the loop's state)
-        select_launch(plan, halt, (restart && i == 0) ? &init : nullptr, d);
+        select_launch(plan, halt, (restart && i == 0) ? &init : nullptr, d, by_rates);
         if (!apply_thresholds(plan, halt, err)) return false;
-        t2_size_launch(plan, true, halt, d, d_rs_out);  // (the summary lands behind the state)
+        t2_size_launch(plan, true, halt, d, d_rs_out, by_rates);  // (the summary lands behind the state)
     }
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(ev[kEvT2End], stream));

@@ -119,11 +119,12 @@ int32_t lossless_layer_frac(int l, int NL) {
 // Rate-control groups of a plan whose tile rows are [tr0, tr1) of an image
 // of `nty` tile rows (P.tile_b0 filled): the -flush_period stripes for a
 // lossless recipe (whole stripes only: a tile-split band is made of them),
-// else one group of every block.
+// else -- and for a lossless recipe encoded by per-layer rates, P.one_group --
+// one group of every block.
 static void rate_groups(Plan &P, int nty_full, int tr0, int tr1) {
     const int nb = (int)P.blocks.size();
     P.grp_b0.assign(1, 0);
-    if (P.rc.rate_bpp <= 0.0 && nb) {
+    if (P.rc.rate_bpp <= 0.0 && nb && !P.one_group) {
         const std::vector<int> ends = flush_stripe_ends(nty_full, P.rc.tile_h, P.h, P.rc.flush_period);
         for (int e : ends)
             if (e > tr0 && e <= tr1) P.grp_b0.push_back(P.tile_b0[(size_t)(e - tr0) * P.ntx]);
@@ -131,6 +132,24 @@ static void rate_groups(Plan &P, int nty_full, int tr0, int tr1) {
     } else {
         P.grp_b0.push_back(nb);
     }
+}
+
+void layer_rate_targets(const Plan &P, const double *rates, int L, int64_t org, int64_t *target, int64_t *budget) {
+    for (int l = 0; l < L; l++) {
+        if (l == L - 1 && P.rc.rate_bpp <= 0.0) {  // the lossless top layer takes every coded pass
+            target[l] = -1;
+            budget[l] = kRateNoBudget;
+            continue;
+        }
+        const int64_t t = (int64_t)std::floor(rates[l] * (double)P.w * (double)P.h / 8.0);
+        target[l] = std::max<int64_t>(0, t - org);
+        // the header estimate: 16 bytes per packet of the layers through l
+        // (for the last layer, the single rate's first budget)
+        const int64_t est = 16 * P.ntileparts + 256 + 16 * (P.npackets / L) * (l + 1);
+        budget[l] = std::max<int64_t>(0, target[l] - est);
+    }
+    // never decreasing with l (equal rates: the estimate grows with the layer)
+    for (int l = L - 2; l >= 0; l--) budget[l] = std::min(budget[l], budget[l + 1]);
 }
 
 BandQuant band_quant(const jp2hip_recipe &rc, int bits, int d, int band) {
@@ -200,7 +219,7 @@ bool resolve_tiles(jp2hip_recipe &rc, int w, int h, std::string &err) {
 }
 
 bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits,
-                std::string &err) {
+                std::string &err, bool one_group) {
     if (w <= 0 || h <= 0 || nc < 1 || nc > 4 || (bits != 8 && bits != 16)) {
         err = "unsupported image geometry (1-4 components, 8 or 16 bits)";
         return false;
@@ -260,6 +279,7 @@ bool build_plan(Plan &P, const jp2hip_recipe &rc, int w, int h, int nc, int bits
     }
     P = Plan();
     P.rc = rc;
+    P.one_group = one_group;
     P.w = w; P.h = h; P.nc = nc; P.bits = bits;
     P.ntx = (int)cdiv(w, rc.tile_w);
     P.nty = (int)cdiv(h, rc.tile_h);
@@ -448,6 +468,7 @@ void split_tile_rows(int nty, int tile_h, int h, int period, int rank, int world
 void make_subplan(const Plan &full, int tr0, int tr1, Plan &S) {
     S = Plan();
     S.rc = full.rc;
+    S.one_group = full.one_group;
     S.w = full.w; S.h = full.h; S.nc = full.nc; S.bits = full.bits;
     S.ntx = full.ntx;
     S.nty = tr1 - tr0;

@@ -692,6 +692,7 @@ struct RateStepArgs {
     int64_t *budget;
     RateState *out_rs;
     T2Summary *out_sum;
+    const int64_t *targets;  // an encode by per-layer rates: a target per layer (rate_step_layers); else null
 };
 // Storage indices of the packets a tile-part sends at places i0 .. i0 + 7 of
 // [.., p1) (SEQ: through the forward map, 8 loads in flight; else the places
@@ -862,7 +863,12 @@ __device__ __forceinline__ void t2_total_body(const T2Args &a, const T2TotalArgs
     }
     if (ta.rate.rs) {
         __syncthreads();  // every field of *sum written
-        if (tid == 0) rate_step(ta.rate.rs, ta.sum, L, ta.rate.budget, ta.rate.out_rs, ta.rate.out_sum);
+        if (tid == 0) {
+            if (ta.rate.targets)
+                rate_step_layers(ta.rate.rs, ta.sum, L, ta.rate.targets, ta.rate.budget, ta.rate.out_rs, ta.rate.out_sum);
+            else
+                rate_step(ta.rate.rs, ta.sum, L, ta.rate.budget, ta.rate.out_rs, ta.rate.out_sum);
+        }
     }
 }
 
@@ -1357,7 +1363,7 @@ bool GpuEncoder::t2_load(const Plan &plan, const T2Tables &T, std::string &err) 
 }
 
 void GpuEncoder::t2_size_launch(const Plan &plan, bool with_kc, const int *halt, RateState *rs,
-                                RateState *out_rs) {
+                                RateState *out_rs, bool by_rates) {
     const int nb = (int)plan.blocks.size();
     T2Args a = t2_args(plan);
     a.halt = halt;
@@ -1366,6 +1372,7 @@ void GpuEncoder::t2_size_launch(const Plan &plan, bool with_kc, const int *halt,
     ra.budget = (int64_t *)budget.ptr;
     ra.out_rs = out_rs;
     ra.out_sum = out_rs ? (T2Summary *)(out_rs + 1) : nullptr;
+    ra.targets = by_rates ? (const int64_t *)ltarget.ptr : nullptr;
     T2TotalArgs ta;
     ta.nblocks = nb;
     ta.lengths = (const int32_t *)lengths.ptr;

@@ -161,6 +161,9 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            # fixed-slope layers and the per-layer report (api.cpp, batch.cpp; the check host only)
            "jp2hip_set_layer_slopes", "jp2hip_batch_set_layer_slopes", "jp2hip_check_layer_slopes",
            "jp2hip_set_layer_report", "jp2hip_layer_report",
+           # explicit per-layer rates (api.cpp, batch.cpp; the check, the step and the targets host only)
+           "jp2hip_set_layer_rates", "jp2hip_batch_set_layer_rates", "jp2hip_check_layer_rates",
+           "jp2hip_layer_rate_step", "jp2hip_layer_rate_targets",
            # device-memory policy (api.cpp; csrc/context.h EncodeEnd)
            "jp2hip_device_bytes", "jp2hip_set_memory_limits", "jp2hip_device_memory", "jp2hip_dma_engines")
 # ... but for the two whose names hold a digit, which the header scan of tests/test_abi.py does not read
@@ -238,6 +241,14 @@ def lib():
     L.jp2hip_set_layer_slopes.argtypes = [c_void_p, POINTER(c_double), c_int32]
     L.jp2hip_batch_set_layer_slopes.argtypes = [c_void_p, POINTER(c_double), c_int32]
     L.jp2hip_check_layer_slopes.argtypes = [POINTER(c_double), c_int32, POINTER(Recipe)]
+    L.jp2hip_set_layer_rates.argtypes = [c_void_p, POINTER(c_double), c_int32]
+    L.jp2hip_batch_set_layer_rates.argtypes = [c_void_p, POINTER(c_double), c_int32]
+    L.jp2hip_check_layer_rates.argtypes = [POINTER(c_double), c_int32, POINTER(Recipe)]
+    L.jp2hip_layer_rate_step.argtypes = [c_int32, c_int32, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64),
+                                         POINTER(c_int64)]
+    L.jp2hip_layer_rate_targets.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(Recipe), c_int32, c_int32,
+                                            POINTER(c_double), c_int32, POINTER(c_int64), POINTER(c_int64),
+                                            POINTER(c_int64)]
     L.jp2hip_slope_from_log2.argtypes = [c_double, c_int32]
     L.jp2hip_slope_from_log2.restype = c_double
     L.jp2hip_slope_to_log2.argtypes = [c_double, c_int32]
@@ -393,6 +404,49 @@ def check_layer_slopes(slopes, rcp: Recipe | None = None) -> None:
     arr, n = slopes_array(slopes)
     if lib().jp2hip_check_layer_slopes(arr, n, byref(rcp) if rcp is not None else None) != 0:
         raise Jp2hipError(last_error())
+
+
+def check_layer_rates(rates, rcp: Recipe | None = None) -> None:
+    """jp2hip_check_layer_rates (no GPU): raises Jp2hipError, naming the
+    entry, for rates jp2hip_set_layer_rates -- or, with ``rcp``, an encode of
+    that recipe -- refuses."""
+    arr, n = slopes_array(rates)
+    if lib().jp2hip_check_layer_rates(arr, n, byref(rcp) if rcp is not None else None) != 0:
+        raise Jp2hipError(last_error())
+
+
+RATE_NO_BUDGET = (1 << 63) - 1  # the budget of a lossless top layer (no target: -1)
+
+
+def layer_rate_step(it: int, fixed: int, part_bytes: int, layer_bytes, targets, budgets):
+    """jp2hip_layer_rate_step (no GPU): one step of the per-layer rate loop
+    after iteration ``it`` sized the code-stream.  Returns (halt, budgets):
+    the budgets as the step leaves them (untouched when it halts)."""
+    n = len(layer_bytes)
+    if len(targets) != n or len(budgets) != n:
+        raise ValueError("layer_bytes, targets and budgets differ in length")
+    lb = (c_int64 * max(1, n))(*layer_bytes)
+    t = (c_int64 * max(1, n))(*targets)
+    b = (c_int64 * max(1, n))(*budgets)
+    rc = int(lib().jp2hip_layer_rate_step(n, it, fixed, part_bytes, lb, t, b))
+    if rc < 0:
+        raise Jp2hipError(last_error())
+    return bool(rc), list(b[:n])
+
+
+def layer_rate_targets(width: int, height: int, components: int, bits: int, rcp: Recipe, rates, letters=0,
+                       tlm: bool | int = 0):
+    """jp2hip_layer_rate_targets (no GPU): (targets, first budgets, info) of an
+    encode of this image by ``rates`` (layer 0 first); info = {"T", "E",
+    "ntileparts", "npackets"}.  Raises for what the encodes refuse."""
+    arr, n = slopes_array(rates)
+    t = (c_int64 * 32)()
+    b = (c_int64 * 32)()
+    info = (c_int64 * 4)()
+    if lib().jp2hip_layer_rate_targets(width, height, components, bits, byref(rcp), tparts_letters(letters),
+                                       int(tlm), arr, n, t, b, info) != 0:
+        raise Jp2hipError(last_error())
+    return list(t[:n]), list(b[:n]), dict(zip(("T", "E", "ntileparts", "npackets"), (int(x) for x in info)))
 
 
 def slope_from_log2(v: float, bits: int) -> float:
@@ -574,6 +628,20 @@ class Encoder:
         fixed slopes off.  Not while the context is encoding."""
         arr, n = slopes_array(slopes)
         if lib().jp2hip_set_layer_slopes(self._h, arr, n) != 0:
+            raise Jp2hipError(last_error())
+
+    def set_layer_rates(self, rates=None):
+        """jp2hip_set_layer_rates, for every later encode on this context and
+        its tile-split peers: ``rates[l]`` (bits per pixel) bounds the
+        code-stream through layer l, layer 0 first and none decreasing --
+        Kakadu's ``-rate`` lists the highest rate first, so ``-rate 3,1.5,0.75``
+        is ``[0.75, 1.5, 3]`` here.  For a lossless recipe the last entry is 0
+        (``-rate -,1.5,0.75`` is ``[0.75, 1.5, 0]``): the top layer takes every
+        coded pass.  ``Recipe.rate_bpp`` is then no target.  None or () turns
+        the rates off; rates and fixed slopes exclude each other.  Not while
+        the context is encoding."""
+        arr, n = slopes_array(rates)
+        if lib().jp2hip_set_layer_rates(self._h, arr, n) != 0:
             raise Jp2hipError(last_error())
 
     def set_layer_report(self, on: bool | int = True):

@@ -110,6 +110,12 @@ class GpuConverter(Converter):
     layers are cut at these thresholds instead of by rate or by fraction
     (Encoder.set_layer_slopes on every context; one per layer of the recipe,
     the last 0 for lossless conversions).
+    ``layer_rates=[r0, r1, ...]`` is Kakadu's ``-rate r1,r2,...`` read from its
+    far end -- layer 0's rate first, where Kakadu lists the highest first --
+    in bits per pixel: every file's code-stream through layer l is held to
+    ``r[l]`` (Encoder.set_layer_rates on every context; one per layer of the
+    recipe, the last 0 for lossless conversions, Kakadu's ``-rate -,...``).
+    It excludes ``layer_slopes``.
 
     Safe for concurrent callers (the reference runs one ImageWorkerVerticle
     thread, MainVerticle.java:229-231; raising that count gives each call its
@@ -122,7 +128,7 @@ class GpuConverter(Converter):
 
     def __init__(self, devices: list[int] | None = None, host_threads: int = 0, per_gpu: int | None = None,
                  split_devices: list[int] | None = None, split_min_pixels: int | None = None, tlm: bool = False,
-                 layer_slopes=None):
+                 layer_slopes=None, layer_rates=None):
         self.tmp_dir = Path(tempfile.gettempdir()) / self.WORKING_DIR_NAME
         self._pool, self._free = [], []
         self._cv = threading.Condition()
@@ -151,6 +157,8 @@ class GpuConverter(Converter):
                     self._split.set_organisation(tlm=True)
                 if layer_slopes is not None:
                     self._split.set_layer_slopes(layer_slopes)
+                if layer_rates is not None:
+                    self._split.set_layer_rates(layer_rates)
                 self._split.split_peers(list(split_devices[1:]), split_min_pixels)
                 self.split_world = len(split_devices)
         except _lib.Jp2hipError as e:
@@ -168,6 +176,14 @@ class GpuConverter(Converter):
             try:
                 for e in self._pool:
                     e.set_layer_slopes(layer_slopes)
+            except _lib.Jp2hipError as e:
+                self.close()
+                raise IOError(BUCKETEER_001.format(f"(GPU converter init: {e})")) from e
+        self.layer_rates = None if layer_rates is None else [float(x) for x in layer_rates]
+        if layer_rates is not None:
+            try:
+                for e in self._pool:
+                    e.set_layer_rates(layer_rates)
             except _lib.Jp2hipError as e:
                 self.close()
                 raise IOError(BUCKETEER_001.format(f"(GPU converter init: {e})")) from e
@@ -190,6 +206,7 @@ class GpuConverter(Converter):
         c._closed = False
         c.tlm = False
         c.layer_slopes = None
+        c.layer_rates = None
         c.unavailable = reason
         return c
 

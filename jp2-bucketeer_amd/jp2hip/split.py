@@ -221,7 +221,8 @@ def encode_split(encoder, d_ptr: int, nbytes: int, layout: Layout, conversion: i
     lengths through ``group`` and rank 0 writes the TLM marker segments;
     ``file_len`` and the later ranks' offsets count them), the same
     ``set_tile_part_divisions``, the same ``set_layer_slopes`` (no threshold
-    is exchanged then) and the same ``set_layer_report`` (the ranks' distortion
+    is exchanged then), the same ``set_layer_rates`` (the ranks run one rate
+    loop over the exchanged per-layer sums) and the same ``set_layer_report`` (the ranks' distortion
     sums travel through ``group``; rank 0's ``layer_report()`` is the image's)."""
     sp = (group or SingleGroup()).split()
     return encoder.encode_device_split(d_ptr, nbytes, layout, conversion, sp, rcp)
