@@ -184,7 +184,8 @@ typedef struct jp2hip_stats {
     double total_ms;      /* host wall time of the call                       */
     double h2d_ms;        /* source upload (encode_file / encode_tiff only)   */
     double ingest_ms;     /* sample expansion (k_expand: sub-byte / palette   */
-                          /* sources only); the strip gather itself is part   */
+                          /* sources only) and orientation (k_orient: only    */
+                          /* with one set); the strip gather itself is part   */
                           /* of dwt_ms (fused into the first DWT level)       */
     double dwt_ms;        /* all DWT kernels                                  */
     double quant_ms;      /* quantisation + bit-plane kernel                  */
@@ -342,6 +343,59 @@ int64_t jp2hip_tile_parts(int32_t width, int32_t height, int32_t components, int
  * < 0 on a null argument or more tile-parts than 256 segments hold. */
 int64_t jp2hip_tlm_segments(const uint16_t *tiles, const uint32_t *lengths, int64_t n,
                             uint8_t *dst, size_t cap);
+
+/* Source orientation: TIFF tag 274 (Orientation), what kdu_compress has
+ * -rotate for.  JP2 has no orientation field that image servers honour, so an
+ * encode that applies the tag writes the upright pixels. */
+#define JP2HIP_ORIENT_OFF 0  /* the default: the rows as they are stored, whatever the tag says */
+                             /* 1 .. 8: that TIFF Orientation (1: the stored image is upright)  */
+#define JP2HIP_ORIENT_TIFF 9 /* the file's own tag 274                                          */
+
+/* The orientation every later encode on ctx applies to its source, its
+ * tile-split peers included (peers added later inherit it).  For a stored
+ * image a of h rows and w columns the upright image is, in numpy's terms,
+ *   1 a              2 a[:, ::-1]      3 a[::-1, ::-1]      4 a[::-1]
+ *   5 a.swapaxes(0, 1)                 6 rot90(a, -1)
+ *   7 a[::-1, ::-1].swapaxes(0, 1)     8 rot90(a, 1)
+ * (5 .. 8: h columns and w rows); pixels move whole, a 16-bit sample keeps
+ * its byte order and a pixel its component order.  The file is the one an
+ * encode with JP2HIP_ORIENT_OFF gives for the uncompressed TIFF of the upright
+ * pixels with the same metadata, byte for byte, on every route and with every
+ * setting: for 5 .. 8 the tiles, SIZ, ihdr, the rate targets and the plan
+ * cache's key take the upright width and height, and the res box has X and Y
+ * resolution exchanged; colr and cdef stay.  The source is decoded and
+ * expanded as always and turned last, on the GPU (DESIGN.md "S1c
+ * orientation"), into a copy that counts in jp2hip_device_bytes and against
+ * the memory limits; JP2HIP_ORIENT_OFF and 1 launch nothing.
+ * JP2HIP_ORIENT_TIFF is resolved where a TIFF is parsed -- jp2hip_encode_file,
+ * jp2hip_encode_tiff, the batch queue -- to the file's tag (absent or
+ * malformed: 1).  jp2hip_encode_device and jp2hip_encode_device_split take a
+ * caller's layout, which names no tag: under JP2HIP_ORIENT_TIFF they are
+ * refused with a message that names this function and
+ * jp2hip_tiff_orientation, and the context stays usable.
+ * Not part of the recipe.  Collective over a caller's callback, like the
+ * organisation: every rank sets the same value.  Not to be called while ctx
+ * is encoding.  Returns 0, or < 0 with a message that names the value. */
+int jp2hip_set_source_orientation(jp2hip_ctx *ctx, int32_t o);
+
+/* Host-only: tag 274 of a TIFF (classic or BigTIFF, either byte order) when it
+ * is one SHORT in 1 .. 8; 1 when the tag is absent or malformed (a bad
+ * metadata tag never fails a parse); < 0 only when `tiff` is no TIFF at all.
+ * Only the first IFD is read (no EXIF sub-IFD). */
+int32_t jp2hip_tiff_orientation(const uint8_t *tiff, size_t len);
+
+/* Host-only: width and height of the upright image of a stored w x h one
+ * (o = 0 .. 8; exchanged for 5 .. 8).  < 0 for another o or a null pointer. */
+int jp2hip_oriented_size(int32_t w, int32_t h, int32_t o, int32_t *ow, int32_t *oh);
+
+/* Host-only, exported for tests (the tile-split uses it): the stored rows
+ * [*src_row0, *src_row1) that rows [row0, row1) of the upright image are made
+ * from -- the same rows for o = 0, 1, 2; the mirrored range height - row1 ..
+ * height - row0 for 3 and 4; every row, 0 .. height, for 5 .. 8.  The range
+ * is clipped to the upright image; an empty one gives an empty one.  < 0 for
+ * another o, a geometry that is not positive or a null pointer. */
+int jp2hip_orientation_source_rows(int32_t height, int32_t width, int32_t o, int32_t row0, int32_t row1,
+                                   int32_t *src_row0, int32_t *src_row1);
 
 /* Fixed-slope quality layers (Kakadu's -slope s1,s2,...): with n =
  * recipe.layers thresholds set, layer 0 first, an encode has no byte target and
@@ -529,7 +583,10 @@ int jp2hip_encoded_format(const jp2hip_layout *layout, int32_t *components, int3
  *     profile -> JPX: the enumerated box, then METH 3 with the profile
  *     (a JP2 reader takes the first box); JP2: the enumerated box alone.
  *   cdef: by extra_samples (above), for 2 or 4 channels.
- *   res : one resc box (capture resolution, points per metre). */
+ *   res : one resc box (capture resolution, points per metre).
+ * The layout is taken as it is: a caller describing a file encoded with a
+ * source orientation of 5 .. 8 passes the upright image's layout -- width and
+ * height exchanged, and xres_* with yres_* -- as the encodes do themselves. */
 int64_t jp2hip_file_header(const jp2hip_layout *layout, int32_t format,
                            uint64_t codestream_bytes, uint8_t *dst, size_t cap);
 
@@ -585,7 +642,14 @@ void jp2hip_split_rows(int32_t height, int32_t tile_h, int32_t flush_period, int
  * just those (with strip offsets relative to it).  Collective: every rank
  * must call it with the same image geometry, recipe and source metadata
  * (extra_samples .. icc_bytes, the profile's bytes included; rank 0 sizes
- * and writes the file header from its own layout). */
+ * and writes the file header from its own layout).
+ * With a source orientation (jp2hip_set_source_orientation, collective too)
+ * the bands are bands of the upright image: jp2hip_split_rows takes the
+ * upright height, and the strips a rank reads are those of
+ * jp2hip_orientation_source_rows of its band -- its mirrored band for 3 and
+ * 4, and for 5 .. 8, where an upright row is a stored column, every strip:
+ * d_src must then hold the whole source on every rank (each decodes it and
+ * turns only the columns of its band). */
 int jp2hip_encode_device_split(jp2hip_ctx *ctx, const void *d_src, size_t src_len,
                                const jp2hip_layout *layout, int conversion,
                                const jp2hip_recipe *recipe, const jp2hip_split *split,
@@ -701,6 +765,9 @@ int jp2hip_batch_set_layer_slopes(jp2hip_batch *b, const double *slopes, int32_t
 /* jp2hip_set_layer_rates on every context of the queue; before the first
  * submit (< 0 after it, or for refused rates). */
 int jp2hip_batch_set_layer_rates(jp2hip_batch *b, const double *rates_bpp, int32_t n);
+/* jp2hip_set_source_orientation on every context of the queue; before the
+ * first submit (< 0 after it, or for a refused value). */
+int jp2hip_batch_set_source_orientation(jp2hip_batch *b, int32_t o);
 /* Queue one image: convert `tiff_path` into `jpx_path` (written atomically)
  * with `conversion` (recipe NULL -> Bucketeer recipe), then upload it under
  * `image_id`.  Never blocks on the GPU; returns < 0 after close. */

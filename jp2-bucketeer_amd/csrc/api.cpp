@@ -36,6 +36,7 @@
 
 #include "context.h"
 #include "encode.h"
+#include "orient_map.h"
 #include "pinned_pool.h"
 #include "source_layout.h"
 
@@ -66,11 +67,22 @@ static PinnedPool &pinned_pool() {
 uint8_t *out_alloc(size_t n) { return pinned_pool().alloc(n); }
 void out_free(void *p) { pinned_pool().free(p); }
 
+// JP2HIP_ORIENT_TIFF is resolved where a TIFF is parsed: the file's own tag
+// (the parse has accepted the file, so the tag reads as 1..8).
+int source_orientation(const jp2hip_ctx *ctx, const uint8_t *tiff, size_t len) {
+    return ctx->orient == JP2HIP_ORIENT_TIFF ? std::max(1, tiff_orientation(tiff, len)) : ctx->orient;
+}
+
 }  // namespace jp2hip
 
 using namespace jp2hip;
 
 namespace {
+
+// jp2hip_encode_device and _split under JP2HIP_ORIENT_TIFF: a caller's layout names no tag
+const char *const kOrientNeedsTiff =
+    "source orientation: JP2HIP_ORIENT_TIFF needs the TIFF itself, and this call takes a caller's layout -- read the "
+    "tag with jp2hip_tiff_orientation and give its value to jp2hip_set_source_orientation";
 
 // Contexts alive in this process (jp2hip_env_check).
 std::atomic<int> g_live_contexts{0};
@@ -260,6 +272,45 @@ int jp2hip_set_organisation(jp2hip_ctx *ctx, const jp2hip_organisation *org) {
     ctx->org = o;
     for (jp2hip_ctx *p : ctx->peers)
         if (jp2hip_set_organisation(p, &o) != 0) return -1;
+    return 0;
+}
+
+int jp2hip_set_source_orientation(jp2hip_ctx *ctx, int32_t o) {
+    if (o < JP2HIP_ORIENT_OFF || o > JP2HIP_ORIENT_TIFF)
+        return fail("source orientation: " + std::to_string(o) + " is neither JP2HIP_ORIENT_OFF (0), a TIFF Orientation " +
+                    "(1 .. 8) nor JP2HIP_ORIENT_TIFF (9)");
+    if (!ctx) return fail("null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    ctx->orient = o;
+    for (jp2hip_ctx *p : ctx->peers)
+        if (jp2hip_set_source_orientation(p, o) != 0) return -1;
+    return 0;
+}
+
+int32_t jp2hip_tiff_orientation(const uint8_t *tiff, size_t len) {
+    const int o = jp2hip::tiff_orientation(tiff, len);
+    return o < 0 ? fail("tiff: not a TIFF file") : o;
+}
+
+int jp2hip_oriented_size(int32_t w, int32_t h, int32_t o, int32_t *ow, int32_t *oh) {
+    if (!ow || !oh) return fail("null argument");
+    if (o < 0 || o > 8) return fail("orientation " + std::to_string(o) + " is outside 0 .. 8");
+    int64_t a, b;
+    jp2hip::orient_size(w, h, o, a, b);
+    *ow = (int32_t)a;
+    *oh = (int32_t)b;
+    return 0;
+}
+
+int jp2hip_orientation_source_rows(int32_t height, int32_t width, int32_t o, int32_t row0, int32_t row1,
+                                   int32_t *src_row0, int32_t *src_row1) {
+    if (!src_row0 || !src_row1) return fail("null argument");
+    if (o < 0 || o > 8) return fail("orientation " + std::to_string(o) + " is outside 0 .. 8");
+    if (height <= 0 || width <= 0) return fail("orientation: bad geometry");
+    int64_t s0, s1;
+    jp2hip::orient_source_rows(height, width, o, row0, row1, s0, s1);
+    *src_row0 = (int32_t)s0;
+    *src_row1 = (int32_t)s1;
     return 0;
 }
 
@@ -505,7 +556,8 @@ int jp2hip_encode_device(jp2hip_ctx *ctx, const void *d_src, size_t src_len, con
     *out_len = 0;
     double t0 = now_ms();
     std::lock_guard<std::mutex> lk(ctx->mu);
-    return encode_core(ctx, d_src, src_len, layout, conversion, recipe, out, out_len, stats, t0, 0.0);
+    if (ctx->orient == JP2HIP_ORIENT_TIFF) return fail(kOrientNeedsTiff);
+    return encode_core(ctx, d_src, src_len, layout, conversion, recipe, out, out_len, stats, t0, 0.0, ctx->orient);
 }
 
 int jp2hip_encode_tiff(jp2hip_ctx *ctx, const uint8_t *tiff, size_t len, int conversion,
@@ -517,14 +569,15 @@ int jp2hip_encode_tiff(jp2hip_ctx *ctx, const uint8_t *tiff, size_t len, int con
     jp2hip_layout lay;
     std::vector<uint64_t> offs;
     if (read_tiff(tiff, len, &lay, offs)) return -1;
+    const int orient = source_orientation(ctx, tiff, len);
     if (wants_split(ctx, lay))
-        return encode_split_host(ctx, tiff, len, lay, conversion, recipe, -1, out, out_len, stats, t0);
+        return encode_split_host(ctx, tiff, len, lay, conversion, recipe, -1, out, out_len, stats, t0, orient);
     std::lock_guard<std::mutex> lk(ctx->mu);
     std::string err;
     double th = now_ms();
     if (!ctx->gpu.upload_source(tiff, len, err)) return fail(err);
     double h2d = now_ms() - th;
-    return encode_core(ctx, ctx->gpu.source(), len, &lay, conversion, recipe, out, out_len, stats, t0, h2d);
+    return encode_core(ctx, ctx->gpu.source(), len, &lay, conversion, recipe, out, out_len, stats, t0, h2d, orient);
 }
 
 int jp2hip_encode_file(jp2hip_ctx *ctx, const char *tiff_path, const char *out_path, int conversion,
@@ -545,7 +598,8 @@ int jp2hip_encode_file(jp2hip_ctx *ctx, const char *tiff_path, const char *out_p
         TempOutput tmp(out_path);
         const int fd = ::open(tmp.name.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0644);
         if (fd < 0) return fail(cannot_write);
-        const int rc = encode_split_host(ctx, mf.p, mf.n, lay, conversion, recipe, fd, nullptr, nullptr, stats, t0);
+        const int rc = encode_split_host(ctx, mf.p, mf.n, lay, conversion, recipe, fd, nullptr, nullptr, stats, t0,
+                                         source_orientation(ctx, mf.p, mf.n));
         const bool closed = ::close(fd) == 0;
         if (rc != 0) return -1;
         return closed && tmp.commit() ? 0 : fail(cannot_write);
@@ -592,6 +646,7 @@ int jp2hip_split_peers(jp2hip_ctx *ctx, const int32_t *ordinals, int32_t n, int6
         p->slopes = ctx->slopes;  // (jp2hip_set_layer_slopes, _rates, jp2hip_set_layer_report likewise)
         p->rates = ctx->rates;
         p->report_on = ctx->report_on;
+        p->orient = ctx->orient;  // (jp2hip_set_source_orientation likewise)
         made.push_back(p);
     }
     for (jp2hip_ctx *p : ctx->peers) jp2hip_destroy(p);
@@ -609,8 +664,9 @@ int jp2hip_encode_device_split(jp2hip_ctx *ctx, const void *d_src, size_t src_le
     *out_len = 0;
     double t0 = now_ms();
     std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->orient == JP2HIP_ORIENT_TIFF) return fail(kOrientNeedsTiff);
     return encode_split_core(ctx, d_src, src_len, layout, conversion, recipe, split, out, out_len, file_offset,
-                             file_len, stats, t0);
+                             file_len, stats, t0, ctx->orient);
 }
 
 void jp2hip_free(void *p) { out_free(p); }

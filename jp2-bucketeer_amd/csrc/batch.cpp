@@ -351,6 +351,13 @@ int jp2hip_batch_set_layer_rates(jp2hip_batch *b, const double *rates_bpp, int32
     return 0;
 }
 
+int jp2hip_batch_set_source_orientation(jp2hip_batch *b, int32_t o) {
+    if (!b || b->submitted_any) return -1;  // (as jp2hip_batch_set_organisation)
+    for (jp2hip_ctx *c : b->ctxs)
+        if (jp2hip_set_source_orientation(c, o) != 0) return -1;  // jp2hip_last_error() holds the reason
+    return 0;
+}
+
 int jp2hip_batch_submit(jp2hip_batch *b, int64_t job, const char *image_id, const char *tiff_path,
                         const char *jpx_path, int conversion, const jp2hip_recipe *recipe) {
     if (!b || !image_id || !tiff_path || !jpx_path || b->closed) return -1;

@@ -58,6 +58,10 @@ struct jp2hip_ctx {
     // are no part of the plan cache's key; that they are set is, for a
     // lossless recipe (PlanCache::one_group)
     std::vector<double> rates;
+    // jp2hip_set_source_orientation: JP2HIP_ORIENT_OFF, 1..8 or
+    // JP2HIP_ORIENT_TIFF, read by every encode, no part of the recipe (the
+    // plan cache's key holds the upright width and height it leads to)
+    int32_t orient = 0;
     int32_t report_on = 0;
     bool report_set = false;
     struct jp2hip_layer_report report{};

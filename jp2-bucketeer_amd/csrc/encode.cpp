@@ -159,9 +159,11 @@ int64_t first_budget_of(const Plan &P, int64_t target) { return target - 16 * P.
 // How both encodes begin: the checks (sp: a split's rank and group), the
 // recipe, what the source states about its pixels (into the file header, per
 // encode: a cached plan is shared by files that differ in it) and the
-// context's per-encode counters; `end` is armed last.
+// context's per-encode counters; `end` is armed last.  orient (0 off, 1..8):
+// tiles and file header are the upright image's -- `up` receives the layout
+// with its width, height and resolution (the strips stay the stored image's).
 int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conversion, const jp2hip_recipe *recipe,
-          const jp2hip_split *sp, jp2hip_recipe &rc, SourceMeta &meta, EncodeEnd &end) {
+          const jp2hip_split *sp, int orient, jp2hip_recipe &rc, SourceMeta &meta, jp2hip_layout &up, EncodeEnd &end) {
     if (conversion != JP2HIP_LOSSY && conversion != JP2HIP_LOSSLESS)
         return fail("conversion must be JP2HIP_LOSSY (0) or JP2HIP_LOSSLESS (1)");
     const int world = sp ? sp->world : 1, rank = sp ? sp->rank : 0;
@@ -169,14 +171,17 @@ int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conv
     if (world > 1 && !sp->allreduce_sum) return fail("split: world > 1 needs an allreduce_sum callback");
     rc = recipe_of(recipe, conversion);
     if (!lay || !d_src) return fail("null source or layout");
+    if (orient < 0 || orient > 8) return fail("source orientation " + std::to_string(orient) + " is outside 0 .. 8");
+    up = *lay;
+    oriented_header(up, orient);
     std::string terr;  // tile_w = tile_h = 0: one tile for this image
-    if (!resolve_tiles(rc, lay->width, lay->height, terr)) return fail(terr);
+    if (!resolve_tiles(rc, up.width, up.height, terr)) return fail(terr);
     // fixed-slope layers: the thresholds against this encode's recipe (refused
     // before the encode begins: the context stays as it was)
     if (!check_layer_slopes(ctx->slopes.data(), (int)ctx->slopes.size(), &rc, terr)) return fail(terr);
     // per-layer rates likewise
     if (!check_layer_rates(ctx->rates.data(), (int)ctx->rates.size(), &rc, terr)) return fail(terr);
-    meta = source_meta(*lay);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
+    meta = source_meta(up);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
     ctx->gpu.take_waits();     // count this encode's host waits (stats)
     ctx->gpu.begin_encode();
     ctx->reused = ctx->ended;  // (stats: how the call before this one ended)
@@ -292,16 +297,20 @@ int finish_part(jp2hip_ctx *ctx, const FilePart &fp, const SourceMeta &meta, std
 // and main headers.
 int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
                 const jp2hip_recipe *recipe, uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start,
-                double h2d_ms) {
+                double h2d_ms, int orient) {
     jp2hip_recipe rc;
     SourceMeta meta;
+    jp2hip_layout up;
     EncodeEnd end;
-    if (begin(ctx, d_src, lay, conversion, recipe, nullptr, rc, meta, end)) return -1;
+    if (begin(ctx, d_src, lay, conversion, recipe, nullptr, orient, rc, meta, up, end)) return -1;
     std::string err;
     jp2hip_layout ulay;
     std::vector<uint64_t> uoffs;
     UnitGrid grid;
-    if (!unit_grid(*lay, grid, err) || !prepare_source(ctx, grid, d_src, src_len, lay, 0, lay->height, ulay, uoffs, err))
+    // (from here on `lay` is the upright image's: the plan, its cache key and
+    // the rate targets see the oriented width and height)
+    if (!unit_grid(*lay, grid, err) ||
+        !prepare_source(ctx, grid, d_src, src_len, lay, 0, up.height, ulay, uoffs, err, orient))
         return fail(err);
     PlanCache &pc = ctx->pc;
     // per-layer rates (jp2hip_set_layer_rates): byte targets for the whole
@@ -453,11 +462,12 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
 // single-GPU file.
 int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
                       const jp2hip_recipe *recipe, const jp2hip_split *sp, uint8_t **out, size_t *out_len,
-                      uint64_t *file_offset, uint64_t *file_len, jp2hip_stats *stats, double t_start) {
+                      uint64_t *file_offset, uint64_t *file_len, jp2hip_stats *stats, double t_start, int orient) {
     jp2hip_recipe rc;
     SourceMeta meta;
+    jp2hip_layout up;  // the upright image's width and height: what the plan and the bands are cut from
     EncodeEnd end;
-    if (begin(ctx, d_src, lay, conversion, recipe, sp, rc, meta, end)) return -1;
+    if (begin(ctx, d_src, lay, conversion, recipe, sp, orient, rc, meta, up, end)) return -1;
     const int world = sp ? sp->world : 1, rank = sp ? sp->rank : 0;
     std::string err;
     auto allreduce = [&](int64_t *v, int n) {
@@ -488,7 +498,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // per-layer rates (collective, like the slopes): a lossless recipe's plan
     // then has one rate-control group, and takes the rate-driven exchange
     const bool by_rates = !ctx->rates.empty();
-    if (!build_plan(full, rc, lay->width, lay->height, enc_nc, enc_bits, err, by_rates && rc.rate_bpp <= 0.0))
+    if (!build_plan(full, rc, up.width, up.height, enc_nc, enc_bits, err, by_rates && rc.rate_bpp <= 0.0))
         return fail(err);
     int tr0, tr1;
     if (untiled(recipe)) {  // one tile row, all of it rank 0's (jp2hip_split_rows with tile_h = 0)
@@ -502,10 +512,13 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     const bool have = sub.ntc > 0;
     // only this rank's rows are read, so only their strips (or tiles) must be
     // in d_src; compressed / tiled units of the band are decoded here (a rank
-    // that fails here still joins every exchange below)
+    // that fails here still joins every exchange below).  With an orientation
+    // the band is one of upright rows: 3 and 4 read the mirrored band's
+    // strips, 5..8 the whole source (prepare_source)
     jp2hip_layout ulay;
     std::vector<uint64_t> uoffs;
-    bool ok = !have || prepare_source(ctx, grid, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err);
+    bool ok = !have ||
+              prepare_source(ctx, grid, d_src, src_len, lay, sub.row0, sub.row0 + sub.band_h, ulay, uoffs, err, orient);
     const bool prof = ctx->cfg.profile != 0;
     StageTimes st;
     std::vector<uint64_t> keys;

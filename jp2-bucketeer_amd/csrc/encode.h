@@ -19,7 +19,8 @@ void out_free(void *p);
 double now_ms();
 // prepare_source.cpp
 bool prepare_source(jp2hip_ctx *ctx, const UnitGrid &g, const void *&d_src, size_t src_len, const jp2hip_layout *&lay,
-                    int row0, int row1, jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err);
+                    int row0, int row1, jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err,
+                    int orient = 0);
 // encode.cpp (the caller holds ctx->mu)
 void default_recipe(jp2hip_recipe *r, int conversion);
 jp2hip_recipe recipe_of(const jp2hip_recipe *recipe, int conversion);
@@ -32,16 +33,20 @@ bool check_layer_slopes(const double *slopes, int n, const jp2hip_recipe *rc, st
 // top layer, no decrease) are refused; with rc also n other than rc->layers, a
 // last entry other than 0 under rate_bpp <= 0 and a 0 entry under rate_bpp > 0.
 bool check_layer_rates(const double *rates, int n, const jp2hip_recipe *rc, std::string &err);
+// orient: the encode's source orientation, resolved (0 off, 1..8: TIFF
+// Orientation; never JP2HIP_ORIENT_TIFF -- the callers that parse a TIFF read
+// its tag, source_orientation())
+int source_orientation(const jp2hip_ctx *ctx, const uint8_t *tiff, size_t len);
 int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
                 const jp2hip_recipe *recipe, uint8_t **out, size_t *out_len, jp2hip_stats *stats, double t_start,
-                double h2d_ms);
+                double h2d_ms, int orient);
 int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip_layout *lay, int conversion,
                       const jp2hip_recipe *recipe, const jp2hip_split *sp, uint8_t **out, size_t *out_len,
-                      uint64_t *file_offset, uint64_t *file_len, jp2hip_stats *stats, double t_start);
+                      uint64_t *file_offset, uint64_t *file_len, jp2hip_stats *stats, double t_start, int orient);
 // split_host.cpp
 bool wants_split(const jp2hip_ctx *ctx, const jp2hip_layout &lay);
 int encode_split_host(jp2hip_ctx *ctx, const uint8_t *file, size_t flen, const jp2hip_layout &lay, int conversion,
                       const jp2hip_recipe *recipe, int fd, uint8_t **out, size_t *out_len, jp2hip_stats *stats,
-                      double t0);
+                      double t0, int orient);
 
 }  // namespace jp2hip

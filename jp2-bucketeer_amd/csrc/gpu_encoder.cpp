@@ -222,6 +222,10 @@ bool GpuEncoder::collect_profile(StageTimes &st, std::string &err) {
         HIPCHECK(hipEventElapsedTime(&t, ev[kEvExpandBegin], ev[kEvExpandEnd]));
         st.ingest += t;
     }
+    if (orient_timed) {
+        HIPCHECK(hipEventElapsedTime(&t, ev[kEvOrientBegin], ev[kEvOrientEnd]));
+        st.ingest += t;
+    }
     HIPCHECK(hipEventElapsedTime(&t, ev[kEvDwtBegin], ev[kEvDwtEnd])); st.dwt = t;
     HIPCHECK(hipEventElapsedTime(&t, ev[kEvDwtEnd], ev[kEvQuantEnd])); st.quant = t;
     HIPCHECK(hipEventElapsedTime(&t, ev[kEvCmBegin], ev[kEvCmEnd])); st.t1_cm = t;

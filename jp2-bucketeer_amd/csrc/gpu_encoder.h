@@ -50,6 +50,8 @@ struct FrontJob;  // front.hip
     X(t2tplen) X(t2tphdr) X(t2tpoff) X(t2blkdst) X(t2out) X(t2sum) X(t2seq)                                   \
     /* S1b sample expansion (expand.hip): the 8-bit copy, its unit offsets and the colour table */           \
     X(expanded) X(exoff) X(exlut)                                                                             \
+    /* S1c orientation (orient.hip): the upright copy and the stored image's strip offsets */                \
+    X(oriented) X(oroff)                                                                                      \
     /* the layer report's per-workgroup distortion sums and their totals (k_layer_dist) */                   \
     X(ldist)                                                                                                  \
     /* an encode by per-layer rates: kMaxLayers targets, then kMaxLayers first budgets (rates_load) */        \
@@ -86,6 +88,7 @@ class GpuEncoder {
     void begin_encode() {
         for (DevBuf *b : bufs()) b->want = 0;
         expand_timed = false;
+        orient_timed = false;
         reuse = 0;
         reuse_front_noted = false;
     }
@@ -125,6 +128,12 @@ class GpuEncoder {
     // row-major strip; enqueued only
     bool expand_samples(const void *d_src, const jp2hip_layout &lay, const UnitGrid &g, const uint32_t *lut,
                         bool profile, const void **d_out, std::string &err);
+
+    // S1c (orient.hip): upright rows [row0, row1) of the image `lay` stores
+    // -- uncompressed strips of 8- or 16-bit samples -- under TIFF Orientation
+    // o = 2..8, into the `oriented` buffer, plane after plane; enqueued only
+    bool orient_samples(const void *d_src, const jp2hip_layout &lay, int o, int row0, int row1, bool profile,
+                        const void **d_out, std::string &err);
 
     // Sums a slope-prediction histogram over the ranks of a tile-split
     // encode, in place; false = exchange failed (or another rank failed).
@@ -275,6 +284,8 @@ class GpuEncoder {
         kEvT2End,
         kEvExpandBegin,  // expand_samples: .. kEvExpandEnd = ingest (k_expand; before kEvFrontBegin)
         kEvExpandEnd,
+        kEvOrientBegin,  // orient_samples: .. kEvOrientEnd = ingest (k_orient_*; before kEvFrontBegin)
+        kEvOrientEnd,
         kNumEvents
     };
     int device = 0;
@@ -299,6 +310,7 @@ class GpuEncoder {
     int64_t *h_tot = nullptr;  // pinned [8]: t1 total, -, k_t1_mq span[2], unpack error, segment tail[2]
     bool profiled = false;
     bool expand_timed = false;  // this encode recorded kEvExpandBegin / End
+    bool orient_timed = false;  // ... kEvOrientBegin / End
     int nseg = 0;  // hull segments at most: the bound sum(3 Mb - 2)
     std::vector<int64_t> h_hist;
     std::vector<uint64_t> strips_host;  // strip offsets last uploaded to `strips`

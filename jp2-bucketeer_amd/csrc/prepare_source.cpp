@@ -4,9 +4,45 @@
 
 #include "context.h"
 #include "encode.h"
+#include "orient_map.h"
 #include "source_layout.h"
 
 namespace jp2hip {
+
+namespace {
+
+// S1c: (d_src, lay) -- the whole stored image as uncompressed strips of whole
+// samples, the entries of the stored rows behind upright rows [row0, row1)
+// valid -- becomes the upright image of TIFF Orientation `orient` (2..8):
+// those rows in the context's `oriented` buffer, and a layout of the upright
+// width and height over them whose resolution follows the axes.  A plane is
+// one strip; a band that starts at row0 > 0 is described by strips of row0
+// rows, so that it starts on a strip and no offset lies in front of the copy.
+bool orient_source(jp2hip_ctx *ctx, const void *&d_src, const jp2hip_layout *&lay, int row0, int row1, int orient,
+                   jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err) {
+    const jp2hip_layout in = *lay;  // (may be ulay, whose table is uoffs: read before either changes)
+    const void *d = nullptr;
+    if (!ctx->gpu.orient_samples(d_src, in, orient, row0, row1, ctx->cfg.profile != 0, &d, err)) return false;
+    const int64_t planes = in.planar == 2 ? in.components : 1;
+    ulay = in;
+    oriented_header(ulay, orient);
+    const uint64_t row_bytes = (uint64_t)ulay.width * (in.planar == 2 ? 1 : in.components) * (in.bits >> 3);
+    const int64_t rps = row0 > 0 ? row0 : ulay.height, per_plane = (ulay.height + rps - 1) / rps;
+    uoffs.assign((size_t)(per_plane * planes), 0);
+    for (int64_t p = 0; p < planes; p++)
+        for (int64_t s = row0 / rps; s <= (row1 - 1) / rps; s++)
+            uoffs[(size_t)(p * per_plane + s)] =
+                (uint64_t)p * (uint64_t)(row1 - row0) * row_bytes + (uint64_t)(s * rps - row0) * row_bytes;
+    ulay.rows_per_strip = (int32_t)rps;
+    ulay.nstrips = (int32_t)(per_plane * planes);
+    ulay.strip_offsets = uoffs.data();
+    ulay.strip_bytes = nullptr;
+    d_src = d;
+    lay = &ulay;
+    return true;
+}
+
+}  // namespace
 
 // What every encode does to its source before the front: the units (strips
 // or tiles; source_layout.h) that image rows [row0, row1) touch are checked
@@ -19,12 +55,24 @@ namespace jp2hip {
 // expansion untiles).  Afterwards (d_src, lay) describe the whole image as
 // uncompressed strips whose entries outside the band are never read (the
 // plan, or a rank's sub-plan, reads only its rows).
+// orient = 2..8 (TIFF Orientation; 0 and 1: nothing more is done): [row0,
+// row1) are rows of the upright image, the units walked, checked and decoded
+// are those of the stored rows behind them (orient_map.h: the mirrored range
+// for 3 and 4, every row for 5..8), and S1c runs last (k_orient, orient.hip):
+// (d_src, lay) then describe the upright image, its width and height, one
+// strip per plane.
 bool prepare_source(jp2hip_ctx *ctx, const UnitGrid &g, const void *&d_src, size_t src_len, const jp2hip_layout *&lay,
-                    int row0, int row1, jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err) {
+                    int row0, int row1, jp2hip_layout &ulay, std::vector<uint64_t> &uoffs, std::string &err, int orient) {
+    const bool turn = orient >= 2;
+    int64_t s0 = row0, s1 = row1;
+    if (turn) orient_source_rows(lay->height, lay->width, orient, row0, row1, s0, s1);
     Band band;
-    if (!band_walk(*lay, g, row0, row1, src_len, band, err)) return false;
+    if (!band_walk(*lay, g, s0, s1, src_len, band, err)) return false;
     const bool expand = needs_expand(*lay);
-    if (!g.tiled && !g.coded && !expand) return true;
+    if (!g.tiled && !g.coded && !expand) {
+        if (!turn) return true;
+        return orient_source(ctx, d_src, lay, row0, row1, orient, ulay, uoffs, err);
+    }
     std::vector<uint64_t> voff, vcnt;
     for (const BandUnit &u : band.units) {
         voff.push_back(u.off);
@@ -87,7 +135,7 @@ bool prepare_source(jp2hip_ctx *ctx, const UnitGrid &g, const void *&d_src, size
     }
     d_src = d;
     lay = &ulay;
-    return true;
+    return !turn || orient_source(ctx, d_src, lay, row0, row1, orient, ulay, uoffs, err);
 }
 
 }  // namespace jp2hip

@@ -65,21 +65,23 @@ struct TiffReader {
     }
 };
 
-}  // namespace
-
-bool parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<uint64_t> &offs, std::string &err) {
-    auto fail = [&err](const std::string &msg) {
+// The file header: the byte order, classic TIFF or BigTIFF, where the first
+// IFD's entries start and how many it holds.  0, or (err says why) 1: not a
+// TIFF at all, 2: a TIFF whose first IFD does not lie inside the file.
+int open_ifd(TiffReader &t, size_t &first, uint64_t &ne, std::string &err) {
+    auto fail = [&err](int rc, const char *msg) {
         err = msg;
-        return false;
+        return rc;
     };
-    if (!buf || len < 8) return fail("tiff: input too short");
-    TiffReader t{buf, len, true};
+    const uint8_t *buf = t.b;
+    const size_t len = t.n;
+    if (!buf || len < 8) return fail(1, "tiff: input too short");
     if (buf[0] == 'I' && buf[1] == 'I') t.le = true;
     else if (buf[0] == 'M' && buf[1] == 'M') t.le = false;
-    else return fail("tiff: bad byte-order mark");
+    else return fail(1, "tiff: bad byte-order mark");
     size_t ifd, ifd_hdr;
     if (t.u16(2) == 43) {  // BigTIFF: offset size 8, reserved 0, first IFD at 8
-        if (t.u16(4) != 8 || t.u16(6) != 0 || len < 16) return fail("tiff: bad BigTIFF header");
+        if (t.u16(4) != 8 || t.u16(6) != 0 || len < 16) return fail(1, "tiff: bad BigTIFF header");
         t.big = true;
         ifd = (size_t)t.u64(8);
         ifd_hdr = 8;
@@ -87,10 +89,44 @@ bool parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<
         ifd = t.u32(4);
         ifd_hdr = 2;
     } else {
-        return fail("tiff: not a TIFF file");
+        return fail(1, "tiff: not a TIFF file");
     }
-    if (ifd + ifd_hdr > len || ifd + ifd_hdr < ifd) return fail("tiff: IFD offset out of range");
-    const uint64_t ne = t.big ? t.u64(ifd) : t.u16(ifd);
+    if (ifd + ifd_hdr > len || ifd + ifd_hdr < ifd) return fail(2, "tiff: IFD offset out of range");
+    ne = t.big ? t.u64(ifd) : t.u16(ifd);
+    first = ifd + ifd_hdr;
+    if (ne > (len - first) / t.entry_size()) return fail(2, "tiff: truncated IFD");
+    return 0;
+}
+
+}  // namespace
+
+int tiff_orientation(const uint8_t *buf, size_t len) {
+    TiffReader t{buf, len, true};
+    size_t first;
+    uint64_t ne;
+    std::string err;
+    const int rc = open_ifd(t, first, ne, err);
+    if (rc) return rc == 1 ? -1 : 1;
+    int o = 1;
+    for (uint64_t i = 0; i < ne; i++) {
+        const size_t e = first + t.entry_size() * (size_t)i;
+        if (t.u16(e) != 274) continue;
+        size_t at;
+        const uint32_t v = t.u16(e + 2) == 3 && t.count(e) == 1 && t.data_at(e, 2, 1, at) ? t.u16(at) : 0;
+        o = v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return o;
+}
+
+bool parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<uint64_t> &offs, std::string &err) {
+    auto fail = [&err](const std::string &msg) {
+        err = msg;
+        return false;
+    };
+    TiffReader t{buf, len, true};
+    size_t first;
+    uint64_t ne;
+    if (open_ifd(t, first, ne, err)) return false;
     uint32_t w = 0, h = 0, spp = 1, bps = 8, comp = 1, planar = 1, rps = 0xFFFFFFFFu, fmt = 1, pred = 1;
     uint32_t photo = 0xFFFFFFFFu;  // absent: inferred from SamplesPerPixel
     uint32_t fill = 1;             // FillOrder: MSB-first when absent
@@ -104,9 +140,8 @@ bool parse_tiff(const uint8_t *buf, size_t len, jp2hip_layout *lay, std::vector<
     uint32_t xr[2] = {0, 0}, yr[2] = {0, 0};
     const uint8_t *icc = nullptr;
     uint64_t icc_bytes = 0;
-    if (ne > (len - ifd - ifd_hdr) / t.entry_size()) return fail("tiff: truncated IFD");
     for (uint64_t i = 0; i < ne; i++) {
-        size_t e = ifd + ifd_hdr + t.entry_size() * (size_t)i;
+        size_t e = first + t.entry_size() * (size_t)i;
         switch (t.u16(e)) {
         case 256: w = (uint32_t)t.val(e, 0); break;
         case 257: h = (uint32_t)t.val(e, 0); break;

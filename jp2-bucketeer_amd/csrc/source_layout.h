@@ -11,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "jp2hip.h"
@@ -32,6 +33,21 @@ inline bool needs_expand(const jp2hip_layout &lay) { return lay.bits < 8 || lay.
 
 // What the code-stream carries for this source (jp2hip_encoded_format).
 void encoded_format(const jp2hip_layout &lay, int &nc, int &bits);
+
+// TIFF Orientation (tag 274) of a file: the tag's value when it is one SHORT
+// in 1..8, 1 when the tag is absent or malformed (a metadata tag never fails
+// a parse) or the IFD cannot be walked, < 0 when `buf` is no TIFF at all.
+int tiff_orientation(const uint8_t *buf, size_t len);
+
+// What the upright image of orientation `o` keeps of a layout that describes
+// the stored one: for 5..8 width and height change places, and X and Y
+// resolution with them.  (The strips still describe the stored image.)
+inline void oriented_header(jp2hip_layout &l, int o) {
+    if (o < 5 || o > 8) return;
+    std::swap(l.width, l.height);
+    std::swap(l.xres_num, l.yres_num);
+    std::swap(l.xres_den, l.yres_den);
+}
 
 // The pixel format of a layout, the parser's or a caller's: the depths,
 // component counts and photometric forms the encoder has a path for.

@@ -14,6 +14,7 @@
 #include "context.h"
 #include "encode.h"
 #include "host_group.h"
+#include "orient_map.h"
 #include "source_layout.h"
 
 namespace jp2hip {
@@ -32,16 +33,21 @@ struct RankResult {
 // TIFF in host memory into pinned memory, upload them to member `m`, run the
 // split encode, and (fd >= 0) write the part at its offset of the output file.
 void split_rank(jp2hip_ctx *m, int rank, int world, HostGroup &grp, const uint8_t *file, size_t flen,
-                const jp2hip_layout &lay, int conversion, const jp2hip_recipe &rc, int fd, double t0,
+                const jp2hip_layout &lay, int conversion, const jp2hip_recipe &rc, int fd, double t0, int orient,
                 RankResult &o) {
     std::memset(&o.st, 0, sizeof o.st);
+    // the rank's band of upright rows, and the stored rows behind it: its own
+    // rows, their mirror (orientation 3, 4) or the whole source (5..8)
+    int64_t ow, oh, s0, s1;
+    orient_size(lay.width, lay.height, orient, ow, oh);
     int r0 = 0, r1 = 0;
-    jp2hip_split_rows(lay.height, rc.tile_h, rc.flush_period, rank, world, &r0, &r1);
-    // what this rank uploads: the units its rows read, whole (the C++ form
+    jp2hip_split_rows((int32_t)oh, rc.tile_h, rc.flush_period, rank, world, &r0, &r1);
+    orient_source_rows(lay.height, lay.width, orient, r0, r1, s0, s1);
+    // what this rank uploads: the units those rows read, whole (the C++ form
     // of jp2hip.split.band_strips)
     UnitGrid grid;
     Band band;
-    if (!unit_grid(lay, grid, o.err) || !band_walk(lay, grid, r0, r1, flen, band, o.err)) {
+    if (!unit_grid(lay, grid, o.err) || !band_walk(lay, grid, s0, s1, flen, band, o.err)) {
         grp.abort();
         return;
     }
@@ -72,7 +78,7 @@ void split_rank(jp2hip_ctx *m, int rank, int world, HostGroup &grp, const uint8_
         } else {
             jp2hip_split sp{rank, world, &HostGroup::call, &grp};
             o.rc = encode_split_core(m, m->gpu.source(), std::max<size_t>(tot, 1), &bl, conversion, &rc, &sp,
-                                     &o.part, &o.part_len, &o.off, &o.flen, &o.st, t0);
+                                     &o.part, &o.part_len, &o.off, &o.flen, &o.st, t0, orient);
             if (o.rc != 0) o.err = jp2hip_last_error();
             grp.abort();  // harmless after the last exchange; wakes the others after a failure
         }
@@ -104,7 +110,7 @@ bool wants_split(const jp2hip_ctx *ctx, const jp2hip_layout &lay) {
 // part) or, fd < 0, into one pinned buffer *out.
 int encode_split_host(jp2hip_ctx *ctx, const uint8_t *file, size_t flen, const jp2hip_layout &lay, int conversion,
                       const jp2hip_recipe *recipe, int fd, uint8_t **out, size_t *out_len, jp2hip_stats *stats,
-                      double t0) {
+                      double t0, int orient) {
     if (conversion != JP2HIP_LOSSY && conversion != JP2HIP_LOSSLESS)
         return fail("conversion must be JP2HIP_LOSSY (0) or JP2HIP_LOSSLESS (1)");
     const jp2hip_recipe rc = recipe_of(recipe, conversion);
@@ -117,9 +123,10 @@ int encode_split_host(jp2hip_ctx *ctx, const uint8_t *file, size_t flen, const j
     std::vector<std::thread> th;
     for (int r = 1; r < world; r++)
         th.emplace_back([&, r] {
-            split_rank(members[(size_t)r], r, world, grp, file, flen, lay, conversion, rc, fd, t0, res[(size_t)r]);
+            split_rank(members[(size_t)r], r, world, grp, file, flen, lay, conversion, rc, fd, t0, orient,
+                       res[(size_t)r]);
         });
-    split_rank(ctx, 0, world, grp, file, flen, lay, conversion, rc, fd, t0, res[0]);
+    split_rank(ctx, 0, world, grp, file, flen, lay, conversion, rc, fd, t0, orient, res[0]);
     for (std::thread &t : th) t.join();
     // report the rank that failed first-hand, not one that saw the abort
     const RankResult *bad = nullptr;

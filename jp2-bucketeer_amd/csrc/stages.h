@@ -1,7 +1,7 @@
 // stages.h -- what the stage files export to GpuEncoder's members: argument
 // structs and launchers of the strip decoders (unpack.hip, lzw.hip), the
-// sample expansion (expand.hip), the fused ingest + DWT (dwt.hip) and tier-1
-// (t1.hip).  Argument structs that only one file uses stay in that file.
+// sample expansion (expand.hip), the orientation (orient.hip), the fused
+// ingest + DWT (dwt.hip) and tier-1 (t1.hip).  Argument structs that only one file uses stay in that file.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,6 +40,25 @@ struct ExpandArgs {
 };
 // false: bits is not 1, 2, 4 (or 8 with a palette), or a launch error
 bool launch_expand(const ExpandArgs &a, int bits, bool palette, hipStream_t st);
+
+// S1c orientation (orient.hip): uncompressed strips of whole-byte elements (a
+// pixel of a chunky source, a sample of a planar one) -> upright rows [row0,
+// row1) of the image under TIFF Orientation o (orient_map.h), row-major, one
+// run of rows per plane.  Row y of plane p starts at
+// src + off[p * spp_strips + y / rps] + (y % rps) * w * es.
+struct OrientArgs {
+    const uint8_t *src;
+    const uint64_t *off;   // [planes * spp_strips] device table
+    int w, h;              // the stored image: elements per row, rows
+    int o;                 // 2..8
+    int rps, spp_strips, planes;
+    int row0, row1;        // upright rows written: dst row 0 is upright row row0
+    uint8_t *dst;          // planes * (row1 - row0) * upright width * es bytes
+};
+constexpr int kOrientTile = 64;  // the transposing form's tile: 64 x 64 elements
+// false: es is not 1, 2, 3, 4, 6 or 8, o is not 2..8, a grid dimension is out
+// of range, or a launch error
+bool launch_orient(const OrientArgs &a, int es, hipStream_t st);
 
 // the SDMA engines chosen per GPU and their probed rates (t2_device.hip)
 std::string dma_engine_report();

@@ -24,6 +24,8 @@ PHOTO_DEFAULT, PHOTO_WHITE_IS_ZERO, PHOTO_PALETTE = 0, 1, 2
 ORDER_LRCP, ORDER_RLCP, ORDER_RPCL, ORDER_PCRL, ORDER_CPRL = 0, 1, 2, 3, 4
 # Stats.reused (JP2HIP_REUSED_*, JP2HIP_AFTER_*): what an encode found in place
 REUSED_PLAN, REUSED_FRONT_TABLES, REUSED_T2_TABLES, REUSED_STRIPS, AFTER_TRIM, AFTER_FAILURE = 1, 2, 4, 8, 16, 32
+# jp2hip_set_source_orientation: off (the default), a TIFF Orientation 1..8, or the file's own tag 274
+ORIENT_OFF, ORIENT_TIFF = 0, 9
 
 
 class Jp2hipError(OSError):
@@ -164,6 +166,9 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            # explicit per-layer rates (api.cpp, batch.cpp; the check, the step and the targets host only)
            "jp2hip_set_layer_rates", "jp2hip_batch_set_layer_rates", "jp2hip_check_layer_rates",
            "jp2hip_layer_rate_step", "jp2hip_layer_rate_targets",
+           # source orientation, TIFF tag 274 (api.cpp, batch.cpp; the tag reader, the size and the rows host only)
+           "jp2hip_set_source_orientation", "jp2hip_batch_set_source_orientation", "jp2hip_tiff_orientation",
+           "jp2hip_oriented_size", "jp2hip_orientation_source_rows",
            # device-memory policy (api.cpp; csrc/context.h EncodeEnd)
            "jp2hip_device_bytes", "jp2hip_set_memory_limits", "jp2hip_device_memory", "jp2hip_dma_engines")
 # ... but for the two whose names hold a digit, which the header scan of tests/test_abi.py does not read
@@ -255,6 +260,13 @@ def lib():
     L.jp2hip_slope_to_log2.restype = c_double
     L.jp2hip_set_layer_report.argtypes = [c_void_p, c_int32]
     L.jp2hip_layer_report.argtypes = [c_void_p, POINTER(LayerReport)]
+    L.jp2hip_set_source_orientation.argtypes = [c_void_p, c_int32]
+    L.jp2hip_batch_set_source_orientation.argtypes = [c_void_p, c_int32]
+    L.jp2hip_tiff_orientation.argtypes = [c_void_p, c_size_t]
+    L.jp2hip_tiff_orientation.restype = c_int32
+    L.jp2hip_oriented_size.argtypes = [c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]
+    L.jp2hip_orientation_source_rows.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32),
+                                                 POINTER(c_int32)]
     L.jp2hip_device_bytes.argtypes = [c_void_p]
     L.jp2hip_device_bytes.restype = c_int64
     L.jp2hip_set_memory_limits.argtypes = [c_void_p, c_int64, c_int64]
@@ -477,6 +489,35 @@ def tlm_segments(tiles, lengths) -> bytes:
     return out.raw[:need]
 
 
+def tiff_orientation(data: bytes) -> int:
+    """TIFF tag 274 (Orientation) of a file (jp2hip_tiff_orientation; no GPU):
+    its value when it is one SHORT in 1..8, 1 when it is absent or malformed.
+    Raises when ``data`` is no TIFF at all."""
+    o = int(lib().jp2hip_tiff_orientation(ctypes.create_string_buffer(data, len(data)), len(data)))
+    if o < 0:
+        raise Jp2hipError(last_error())
+    return o
+
+
+def oriented_size(width: int, height: int, o: int) -> tuple[int, int]:
+    """(width, height) of the upright image of a stored width x height one
+    under orientation ``o`` (jp2hip_oriented_size; no GPU)."""
+    ow, oh = c_int32(), c_int32()
+    if lib().jp2hip_oriented_size(width, height, o, byref(ow), byref(oh)) != 0:
+        raise Jp2hipError(last_error())
+    return ow.value, oh.value
+
+
+def orientation_source_rows(height: int, width: int, o: int, row0: int, row1: int) -> tuple[int, int]:
+    """The stored rows [s0, s1) that rows [row0, row1) of the upright image
+    are made from (jp2hip_orientation_source_rows; no GPU): what a tile-split
+    rank passes to ``split.band_strips`` for its band of upright rows."""
+    s0, s1 = c_int32(), c_int32()
+    if lib().jp2hip_orientation_source_rows(height, width, o, row0, row1, byref(s0), byref(s1)) != 0:
+        raise Jp2hipError(last_error())
+    return s0.value, s1.value
+
+
 def tiff_layout(data: bytes):
     """Parse a baseline TIFF header; returns (Layout, offsets array).  The
     Layout owns copies of the file's ICC profile and ColorMap (Layout.icc and
@@ -642,6 +683,17 @@ class Encoder:
         the context is encoding."""
         arr, n = slopes_array(rates)
         if lib().jp2hip_set_layer_rates(self._h, arr, n) != 0:
+            raise Jp2hipError(last_error())
+
+    def set_source_orientation(self, o: int = ORIENT_OFF):
+        """jp2hip_set_source_orientation, for every later encode on this
+        context and its tile-split peers: ORIENT_OFF (the default: the rows as
+        stored, whatever the tag says), a TIFF Orientation 1..8, or
+        ORIENT_TIFF, the file's own tag 274 (encode_file, encode_tiff and the
+        batch queue; encode_device takes a layout and is refused under it --
+        read the tag with ``tiff_orientation`` and set its value).  The file
+        holds the upright pixels.  Not while the context is encoding."""
+        if lib().jp2hip_set_source_orientation(self._h, int(o)) != 0:
             raise Jp2hipError(last_error())
 
     def set_layer_report(self, on: bool | int = True):

@@ -116,6 +116,11 @@ class GpuConverter(Converter):
     ``r[l]`` (Encoder.set_layer_rates on every context; one per layer of the
     recipe, the last 0 for lossless conversions, Kakadu's ``-rate -,...``).
     It excludes ``layer_slopes``.
+    ``orientation=`` is the source orientation every context applies
+    (Encoder.set_source_orientation): ``ORIENT_OFF``, the default, writes the
+    rows as the TIFF stores them, as kdu_compress does without ``-rotate``;
+    ``ORIENT_TIFF`` honours each file's own Orientation tag (274), 1..8 apply
+    that value to every file.  The JPX holds the upright pixels.
 
     Safe for concurrent callers (the reference runs one ImageWorkerVerticle
     thread, MainVerticle.java:229-231; raising that count gives each call its
@@ -128,7 +133,7 @@ class GpuConverter(Converter):
 
     def __init__(self, devices: list[int] | None = None, host_threads: int = 0, per_gpu: int | None = None,
                  split_devices: list[int] | None = None, split_min_pixels: int | None = None, tlm: bool = False,
-                 layer_slopes=None, layer_rates=None):
+                 layer_slopes=None, layer_rates=None, orientation: int = _lib.ORIENT_OFF):
         self.tmp_dir = Path(tempfile.gettempdir()) / self.WORKING_DIR_NAME
         self._pool, self._free = [], []
         self._cv = threading.Condition()
@@ -159,6 +164,8 @@ class GpuConverter(Converter):
                     self._split.set_layer_slopes(layer_slopes)
                 if layer_rates is not None:
                     self._split.set_layer_rates(layer_rates)
+                if orientation != _lib.ORIENT_OFF:
+                    self._split.set_source_orientation(orientation)
                 self._split.split_peers(list(split_devices[1:]), split_min_pixels)
                 self.split_world = len(split_devices)
         except _lib.Jp2hipError as e:
@@ -187,6 +194,14 @@ class GpuConverter(Converter):
             except _lib.Jp2hipError as e:
                 self.close()
                 raise IOError(BUCKETEER_001.format(f"(GPU converter init: {e})")) from e
+        self.orientation = int(orientation)
+        if orientation != _lib.ORIENT_OFF:
+            try:
+                for e in self._pool:
+                    e.set_source_orientation(orientation)
+            except _lib.Jp2hipError as e:
+                self.close()
+                raise IOError(BUCKETEER_001.format(f"(GPU converter init: {e})")) from e
         self._free = list(self._pool)
         # the slow configurations the library can see (queues, SDMA): logged once
         self.env_advice = _lib.env_check()
@@ -207,6 +222,7 @@ class GpuConverter(Converter):
         c.tlm = False
         c.layer_slopes = None
         c.layer_rates = None
+        c.orientation = _lib.ORIENT_OFF
         c.unavailable = reason
         return c
 

@@ -149,6 +149,10 @@ def thresholds(keys, cum, budgets, group: _Group | None = None) -> np.ndarray:
 def band_strips(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
     """The strips a rank reads for image rows [row0, row1), packed back to back.
 
+    With a source orientation the rows are stored rows: those
+    ``jp2hip.orientation_source_rows`` names for the rank's band of upright
+    rows (the mirrored band for 3 and 4; every row for 5..8).
+
     Returns (buffer, Layout, offsets) with offsets rebased to the buffer, so a
     rank uploads only its band of a multi-GB TIFF.  Offsets of strips outside
     the band are 0 and never read (front.hip k_ingest / dwt.hip band_load
