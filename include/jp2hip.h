@@ -489,6 +489,94 @@ int jp2hip_layer_rate_targets(int32_t width, int32_t height, int32_t components,
                               const double *rates_bpp, int32_t n, int64_t *targets, int64_t *budgets,
                               int64_t *info);
 
+/* Quality layers by target PSNR (OpenJPEG's -q q1,q2,...): with n =
+ * recipe.layers targets set, in dB and layer 0 first, layer l is the smallest
+ * selection whose predicted PSNR is at least psnr_db[l] -- the highest slope
+ * threshold, the fewest hull segments, that reaches it.  An encode has no byte
+ * target and no rate loop: the thresholds are found on the device in one
+ * selection, and what follows is the fixed-slope encode at those thresholds
+ * (the file is the one jp2hip_set_layer_slopes gives at
+ * jp2hip_layer_report.threshold).  NULL / n = 0 turns it off.
+ *   - The predicted PSNR of a layer is 10 log10(peak^2 * N / D): peak =
+ *     2^bits - 1, N = width * height * components of jp2hip_encoded_format
+ *     (the upright size under an orientation), D the distortion the layer
+ *     leaves as jp2hip_layer_report defines it -- over the code-blocks, the
+ *     band's weight times the squared-error decrease of the coding passes the
+ *     layer does not hold.  Like the report's, D is exact (against a decoder's
+ *     summed squared error) where the transform is orthogonal -- levels = 0 --
+ *     and an estimate otherwise.  The irreversible path's
+ *     quantisation error is no part of it: D counts what the passes left out
+ *     would have removed, so a layer that holds every pass predicts D = 0
+ *     where a decoder still sees the quantiser's error.
+ *   - D is summed in integer quanta, not in doubles, so that the selection is
+ *     exact and the same on every route (jp2hip_distortion_quantum); a layer
+ *     meets its target when the quanta it leaves are at most
+ *     jp2hip_layer_psnr_targets' integer.  Only segments of the blocks' convex
+ *     hulls count: passes behind a hull's last point remove nothing.
+ *   - A target so low that no pass is needed takes nothing (the threshold is
+ *     one above the largest slope key, as a byte budget of 0 gives); the whole
+ *     hull leaves no quanta, so every target is reached by some selection, and
+ *     threshold 0 is the lossless top layer's alone.
+ *   - recipe.rate_bpp is no target.  > 0 only selects the irreversible
+ *     recipe's meaning of "not lossless", and every target must be finite and
+ *     > 0.  With rate_bpp <= 0 the last layer takes every coded pass and its
+ *     entry must be 0 (a lossless top layer).
+ *   - recipe.slope_skip is ignored: every bit-plane is coded, as with slopes.
+ *   - stats.rate_iterations = 0; the Kdu-Layer-Info lines print the thresholds
+ *     found.
+ *   - A lossless recipe's plan has one rate-control group while targets are
+ *     set, exactly as with layer rates (a quality target is the whole
+ *     image's); the plan cache's key holds that, not the targets.
+ *   - PSNR targets, fixed-slope layers and per-layer rates exclude one
+ *     another: setting one while another is set is refused.
+ *   - Collective like the slopes: peers of jp2hip_split_peers get the targets
+ *     here and inherit them when added later; over a caller's callback every
+ *     rank sets the same targets.  The ranks agree on the thresholds through
+ *     jp2hip_split_psnr_thresholds; the parts concatenate to the single-GPU file.
+ *   - An image whose quanta could overflow 63 bits is refused at the encode
+ *     with a message (a bound over the plan's code-blocks).
+ * Refused, with a message that names the entry (or the other setter): a NaN,
+ * an infinity, a negative value, a sequence that decreases anywhere (a last 0
+ * is the lossless top layer, no decrease), n outside 0..32; at the encode, n
+ * other than the recipe's layers, with rate_bpp <= 0 a last entry other than
+ * 0, with rate_bpp > 0 an entry of 0 (the context stays usable).  Not to be
+ * called while ctx is encoding. */
+int jp2hip_set_layer_psnr(jp2hip_ctx *ctx, const double *psnr_db, int32_t n);
+
+/* Host-only: the checks above on their own -- those of the encode too when
+ * `recipe` is given.  Returns 0, or < 0 with a message that names the entry. */
+int jp2hip_check_layer_psnr(const double *psnr_db, int32_t n, const jp2hip_recipe *recipe);
+
+/* Host-only, exported for tests: the integer one hull segment -- a distortion
+ * decrease dd (tier-1's unit) in a code-block of PCRD weight `weight` --
+ * contributes to the selection above, the text the kernels compile:
+ *     q = floor((weight * (double)dd) * 2^-s + 0.5),  s = 2 * (bits - 8) - 8,
+ * saturated at 2^63 - 1, and 0 where the product is not positive.  A quantum is
+ * 2^s squared sample levels: 1/256 of a squared level at 8 bits, the same share
+ * of the squared range at every depth.  (double)dd and the product round to
+ * nearest; the scale is a power of two; numpy's float64 gives the same bits.
+ * < 0 with a message for bits outside 1..16. */
+int64_t jp2hip_distortion_quantum(double weight, int64_t dd, int32_t bits);
+
+/* Host-only, exported for tests: the quanta each layer may leave,
+ * targets[l] = floor(peak^2 * N * 2^-s / 10^(psnr_db[l] / 10)) with N = width *
+ * height * components (saturated at 2^62), and -1 for a last entry of 0, the
+ * lossless top layer.  The encodes use this function and nothing else to
+ * convert dB.  < 0 with a message for a bad geometry or refused targets. */
+int jp2hip_layer_psnr_targets(int32_t width, int32_t height, int32_t components, int32_t bits,
+                              const double *psnr_db, int32_t n, int64_t *targets);
+
+/* Host-only: 1 when an encode of this image and recipe by PSNR targets is
+ * accepted, 0 when it is refused because its quanta could overflow 63 bits,
+ * < 0 with a message for a geometry or recipe no encode takes.  The bound adds,
+ * over the plan's code-blocks, weight * 8 * w * h * 4^Mb * 2^-s + (3 Mb - 2); it
+ * is loose by the guard bits and the range margin in Mb.  With the default
+ * recipes it accepts about 1.25 * 10^9 samples of an RGB image (some 418
+ * megapixels, 20 000 x 20 000) and 1.8 * 10^9 of a grey one (lossless; lossy
+ * 1.4 and 4.1 * 10^9), at 8 and at 16 bits alike. */
+int jp2hip_layer_psnr_fits(int32_t width, int32_t height, int32_t components, int32_t bits,
+                           const jp2hip_recipe *recipe);
+
 /* Kdu-Layer-Info's number <-> a threshold for `bits`-bit samples:
  * s = 2^(v + 2 * bits). */
 double jp2hip_slope_from_log2(double v, int32_t bits);
@@ -686,6 +774,22 @@ int jp2hip_split_thresholds(const uint64_t *keys, const int64_t *cum, int64_t ns
                             const int64_t *budgets, int32_t layers, const jp2hip_split *split,
                             uint64_t *K);
 
+/* Host-only: the same exchange for quality layers by target PSNR
+ * (jp2hip_set_layer_psnr), exported for tests -- this rank's hull segments as
+ * slope keys descending and inclusive sums of distortion quanta
+ * (jp2hip_distortion_quantum), targets as jp2hip_layer_psnr_targets gives them.
+ * With need[l] = (sum over ranks of all quanta) - targets[l],
+ * K[l] = max{k : sum over ranks of quanta with key >= k >= need[l]}: the tie
+ * group at K[l] is taken.  need[l] <= 0 takes nothing: K[l] is one above the
+ * largest key of all ranks (0 when no rank has a segment).  A need the total
+ * does not reach (targets[l] < 0, the lossless top layer) gives K[l] = 0.
+ * Collective: every rank calls it with the same targets, a rank without
+ * segments with nseg = 0.  Returns 0, -1 for a bad argument, -2 when the
+ * all-reduce failed. */
+int jp2hip_split_psnr_thresholds(const uint64_t *keys, const int64_t *cum_quanta, int64_t nseg,
+                                 const int64_t *targets, int32_t layers, const jp2hip_split *split,
+                                 uint64_t *K);
+
 /* Host-only: the packets of tile `tile` (raster index) of a width x height
  * image of `components` x `bits`-bit samples, in the order recipe->progression
  * sends them -- the function the encodes lay their tile-parts out with,
@@ -765,6 +869,9 @@ int jp2hip_batch_set_layer_slopes(jp2hip_batch *b, const double *slopes, int32_t
 /* jp2hip_set_layer_rates on every context of the queue; before the first
  * submit (< 0 after it, or for refused rates). */
 int jp2hip_batch_set_layer_rates(jp2hip_batch *b, const double *rates_bpp, int32_t n);
+/* jp2hip_set_layer_psnr on every context of the queue; before the first
+ * submit (< 0 after it, or for refused targets). */
+int jp2hip_batch_set_layer_psnr(jp2hip_batch *b, const double *psnr_db, int32_t n);
 /* jp2hip_set_source_orientation on every context of the queue; before the
  * first submit (< 0 after it, or for a refused value). */
 int jp2hip_batch_set_source_orientation(jp2hip_batch *b, int32_t o);

@@ -38,6 +38,7 @@
 #include "encode.h"
 #include "orient_map.h"
 #include "pinned_pool.h"
+#include "psnr_quantum.h"
 #include "source_layout.h"
 
 namespace jp2hip {
@@ -351,6 +352,8 @@ int jp2hip_set_layer_slopes(jp2hip_ctx *ctx, const double *slopes, int32_t n) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (n && !ctx->rates.empty())
         return fail("layer slopes: per-layer rates are set on this context (jp2hip_set_layer_rates); turn them off first");
+    if (n && !ctx->psnr.empty())
+        return fail("layer slopes: PSNR targets are set on this context (jp2hip_set_layer_psnr); turn them off first");
     ctx->slopes.assign(slopes, slopes + n);
     for (jp2hip_ctx *p : ctx->peers)
         if (jp2hip_set_layer_slopes(p, slopes, n) != 0) return -1;
@@ -369,10 +372,60 @@ int jp2hip_set_layer_rates(jp2hip_ctx *ctx, const double *rates_bpp, int32_t n) 
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (n && !ctx->slopes.empty())
         return fail("layer rates: fixed-slope layers are set on this context (jp2hip_set_layer_slopes); turn them off first");
+    if (n && !ctx->psnr.empty())
+        return fail("layer rates: PSNR targets are set on this context (jp2hip_set_layer_psnr); turn them off first");
     ctx->rates.assign(rates_bpp, rates_bpp + n);
     for (jp2hip_ctx *p : ctx->peers)
         if (jp2hip_set_layer_rates(p, rates_bpp, n) != 0) return -1;
     return 0;
+}
+
+int jp2hip_check_layer_psnr(const double *psnr_db, int32_t n, const jp2hip_recipe *recipe) {
+    std::string err;
+    return jp2hip::check_layer_psnr(psnr_db, n, recipe, err) ? 0 : fail(err);
+}
+
+int jp2hip_set_layer_psnr(jp2hip_ctx *ctx, const double *psnr_db, int32_t n) {
+    if (!psnr_db) n = 0;
+    if (jp2hip_check_layer_psnr(psnr_db, n, nullptr) != 0) return -1;
+    if (!ctx) return fail("null context");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (n && !ctx->slopes.empty())
+        return fail("layer psnr: fixed-slope layers are set on this context (jp2hip_set_layer_slopes); turn them off first");
+    if (n && !ctx->rates.empty())
+        return fail("layer psnr: per-layer rates are set on this context (jp2hip_set_layer_rates); turn them off first");
+    ctx->psnr.assign(psnr_db, psnr_db + n);
+    for (jp2hip_ctx *p : ctx->peers)
+        if (jp2hip_set_layer_psnr(p, psnr_db, n) != 0) return -1;
+    return 0;
+}
+
+int64_t jp2hip_distortion_quantum(double weight, int64_t dd, int32_t bits) {
+    if (bits < 1 || bits > 16) return fail("distortion quantum: bits = " + std::to_string(bits) + " is outside 1 .. 16");
+    return jp2hip::distortion_quantum(weight, dd, bits);
+}
+
+int jp2hip_layer_psnr_targets(int32_t width, int32_t height, int32_t components, int32_t bits, const double *psnr_db,
+                              int32_t n, int64_t *targets) {
+    if (!targets) return fail("null argument");
+    if (width <= 0 || height <= 0 || components < 1 || components > 4 || bits < 1 || bits > 16)
+        return fail("layer psnr: bad geometry (1-4 components, 1-16 bits)");
+    std::string err;
+    if (!jp2hip::check_layer_psnr(psnr_db, n, nullptr, err)) return fail(err);
+    jp2hip::layer_psnr_targets(width, height, components, bits, psnr_db, n, targets);
+    return 0;
+}
+
+int jp2hip_layer_psnr_fits(int32_t width, int32_t height, int32_t components, int32_t bits,
+                           const jp2hip_recipe *recipe) {
+    if (!recipe) return fail("null argument");
+    jp2hip::Plan plan;
+    std::string err;
+    jp2hip_recipe rc = *recipe;
+    if (!jp2hip::resolve_tiles(rc, width, height, err) ||
+        !jp2hip::build_plan(plan, rc, width, height, components, bits, err, rc.rate_bpp <= 0.0))
+        return fail(err);
+    return jp2hip::quanta_fit(plan) ? 1 : 0;
 }
 
 int jp2hip_layer_rate_step(int32_t layers, int32_t it, int64_t fixed, int64_t part_bytes, const int64_t *layer_bytes,
@@ -643,8 +696,9 @@ int jp2hip_split_peers(jp2hip_ctx *ctx, const int32_t *ordinals, int32_t n, int6
         }
         p->org = ctx->org;  // (jp2hip_set_organisation: peers added later inherit it)
         p->tparts = ctx->tparts;  // (jp2hip_set_tile_part_divisions likewise)
-        p->slopes = ctx->slopes;  // (jp2hip_set_layer_slopes, _rates, jp2hip_set_layer_report likewise)
+        p->slopes = ctx->slopes;  // (jp2hip_set_layer_slopes, _rates, _psnr, jp2hip_set_layer_report likewise)
         p->rates = ctx->rates;
+        p->psnr = ctx->psnr;
         p->report_on = ctx->report_on;
         p->orient = ctx->orient;  // (jp2hip_set_source_orientation likewise)
         made.push_back(p);

@@ -351,6 +351,13 @@ int jp2hip_batch_set_layer_rates(jp2hip_batch *b, const double *rates_bpp, int32
     return 0;
 }
 
+int jp2hip_batch_set_layer_psnr(jp2hip_batch *b, const double *psnr_db, int32_t n) {
+    if (!b || b->submitted_any) return -1;  // (as jp2hip_batch_set_organisation)
+    for (jp2hip_ctx *c : b->ctxs)
+        if (jp2hip_set_layer_psnr(c, psnr_db, n) != 0) return -1;  // jp2hip_last_error() holds the reason
+    return 0;
+}
+
 int jp2hip_batch_set_source_orientation(jp2hip_batch *b, int32_t o) {
     if (!b || b->submitted_any) return -1;  // (as jp2hip_batch_set_organisation)
     for (jp2hip_ctx *c : b->ctxs)

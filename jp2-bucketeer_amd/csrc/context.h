@@ -58,6 +58,11 @@ struct jp2hip_ctx {
     // are no part of the plan cache's key; that they are set is, for a
     // lossless recipe (PlanCache::one_group)
     std::vector<double> rates;
+    // jp2hip_set_layer_psnr: the predicted PSNR (dB) each layer must reach
+    // (empty: off; excludes slopes and rates), read by every encode.  As with
+    // the rates, that targets are set is part of the plan cache's key for a
+    // lossless recipe (PlanCache::one_group), the targets are not
+    std::vector<double> psnr;
     // jp2hip_set_source_orientation: JP2HIP_ORIENT_OFF, 1..8 or
     // JP2HIP_ORIENT_TIFF, read by every encode, no part of the recipe (the
     // plan cache's key holds the upright width and height it leads to)

@@ -12,6 +12,10 @@
 // With per-layer rates (jp2hip_set_layer_rates) both loops run with a target
 // and a budget per layer and one step, layer_rate_step (jp2hip_internal.h),
 // also for a lossless recipe, whose plan then has one rate-control group.
+// With PSNR targets (jp2hip_set_layer_psnr) neither loop runs either: the
+// thresholds come from one selection over distortion quanta -- on the device
+// (GpuEncoder::select_psnr) or, in a split, agreed through
+// jp2hip_split_psnr_thresholds -- and the rest is the fixed-slope encode.
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
@@ -21,6 +25,7 @@
 
 #include "context.h"
 #include "encode.h"
+#include "psnr_quantum.h"
 #include "source_layout.h"
 
 namespace jp2hip {
@@ -128,6 +133,72 @@ bool check_layer_rates(const double *r, int n, const jp2hip_recipe *rc, std::str
     return true;
 }
 
+bool check_layer_psnr(const double *p, int n, const jp2hip_recipe *rc, std::string &err) {
+    if (n < 0 || n > kMaxLayers || (n > 0 && !p)) {
+        err = "layer psnr: n = " + std::to_string(n) + " is outside 0 .. " + std::to_string(kMaxLayers) +
+              " (or no targets were given)";
+        return false;
+    }
+    for (int i = 0; i < n; i++) {
+        const std::string at = "layer psnr: psnr_db[" + std::to_string(i) + "]";
+        if (std::isnan(p[i])) err = at + " is NaN";
+        else if (std::isinf(p[i])) err = at + " is infinite";
+        else if (std::signbit(p[i])) err = at + " = " + std::to_string(p[i]) + " is negative";
+        else if (i && p[i] < p[i - 1] && !(i == n - 1 && p[i] == 0.0))
+            err = at + " decreases from psnr_db[" + std::to_string(i - 1) + "]: the targets rise from layer 0 on";
+        else continue;
+        return false;
+    }
+    if (!rc || !n) return true;
+    if (n != rc->layers) {
+        err = "layer psnr: n = " + std::to_string(n) + " targets for an encode of recipe.layers = " +
+              std::to_string(rc->layers);
+        return false;
+    }
+    if (rc->rate_bpp <= 0.0 && p[n - 1] != 0.0) {
+        err = "layer psnr: psnr_db[" + std::to_string(n - 1) + "], the last, must be 0 with rate_bpp <= 0 " +
+              "(the last layer takes every coded pass)";
+        return false;
+    }
+    for (int i = 0; i < n && rc->rate_bpp > 0.0; i++)
+        if (p[i] == 0.0) {
+            err = "layer psnr: psnr_db[" + std::to_string(i) + "] is 0 with rate_bpp > 0 (0 names a lossless top layer: " +
+                  "rate_bpp <= 0)";
+            return false;
+        }
+    return true;
+}
+
+void layer_psnr_targets(int width, int height, int components, int bits, const double *psnr_db, int n,
+                        int64_t *targets) {
+    const double peak = std::ldexp(1.0, bits) - 1.0;
+    // peak^2 N 2^-s: exact in a double up to 2^53, which a 2^29-sample image reaches
+    const double full = peak * peak * ((double)width * (double)height * (double)components) *
+                        quantum_pow2(-quantum_shift(bits));
+    for (int l = 0; l < n; l++) {
+        if (l == n - 1 && psnr_db[l] == 0.0) {  // the lossless top layer takes every coded pass
+            targets[l] = -1;
+            continue;
+        }
+        const double t = std::floor(full / std::pow(10.0, psnr_db[l] / 10.0));
+        targets[l] = t >= (double)kQuantaTargetMax ? kQuantaTargetMax : (int64_t)t;
+    }
+}
+
+// An upper bound on the quanta of a plan's hull segments (psnr_quantum.h has
+// the reasoning): false when it reaches 2^63, an image whose sums could
+// overflow and which an encode by PSNR targets therefore refuses.
+bool quanta_fit(const Plan &P) {
+    const double scale = quantum_pow2(-quantum_shift(P.bits));
+    double sum = 0.0;
+    for (size_t b = 0; b < P.blocks.size(); b++) {
+        const BlockDesc &d = P.blocks[b];
+        sum += P.weight[b] * 8.0 * (double)d.w * (double)d.h * std::ldexp(1.0, 2 * d.Mb) * scale +
+               (double)std::max(0, 3 * d.Mb - 2);
+    }
+    return sum < kQuantaLimit;
+}
+
 namespace {
 
 // The slope keys of a context's thresholds: the doubles' bit patterns.
@@ -181,6 +252,8 @@ int begin(jp2hip_ctx *ctx, const void *d_src, const jp2hip_layout *lay, int conv
     if (!check_layer_slopes(ctx->slopes.data(), (int)ctx->slopes.size(), &rc, terr)) return fail(terr);
     // per-layer rates likewise
     if (!check_layer_rates(ctx->rates.data(), (int)ctx->rates.size(), &rc, terr)) return fail(terr);
+    // PSNR targets likewise
+    if (!check_layer_psnr(ctx->psnr.data(), (int)ctx->psnr.size(), &rc, terr)) return fail(terr);
     meta = source_meta(up);  // (a split: rank 0's file header; equal on all ranks, jp2hip.h)
     ctx->gpu.take_waits();     // count this encode's host waits (stats)
     ctx->gpu.begin_encode();
@@ -317,7 +390,10 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     // image, so a lossless recipe's plan has one rate-control group, not the
     // flush stripes -- part of the cache's key (the rates themselves are not)
     const bool by_rates = !ctx->rates.empty();
-    const bool one_group = by_rates && rc.rate_bpp <= 0.0;
+    // PSNR targets (jp2hip_set_layer_psnr): a quality target is the whole
+    // image's too -- the same bit of the key
+    const bool by_psnr = !ctx->psnr.empty();
+    const bool one_group = (by_rates || by_psnr) && rc.rate_bpp <= 0.0;
     if (!pc.valid || pc.w != lay->width || pc.h != lay->height || pc.nc != lay->components || pc.bits != lay->bits ||
         pc.one_group != one_group || std::memcmp(&pc.rc, &rc, sizeof rc) != 0) {
         pc.valid = false;
@@ -355,7 +431,15 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     // predicted and every plane is coded
     const bool fixed = !ctx->slopes.empty();
     const std::vector<uint64_t> keys = slope_keys(ctx->slopes);
-    int64_t skip_target = fixed ? -1 : skip_target_of(rc, plan.w, plan.h, tlm + E);
+    int64_t skip_target = fixed || by_psnr ? -1 : skip_target_of(rc, plan.w, plan.h, tlm + E);
+    // PSNR targets: the quanta each layer may leave; the hulls then come with
+    // their histogram of quanta (set_psnr holds for this encode's run_front)
+    int64_t qtarget[kMaxLayers] = {};
+    if (by_psnr) {
+        if (!quanta_fit(plan)) return fail("layer psnr: the distortion quanta of an image this large could overflow 63 bits");
+        layer_psnr_targets(plan.w, plan.h, plan.nc, plan.bits, ctx->psnr.data(), rc.layers, qtarget);
+    }
+    ctx->gpu.set_psnr(by_psnr ? plan.bits : 0);
     // per-layer rates: every layer's target and first budget;
     // slope prediction aims at the top layer's target, the largest (a
     // lossless top layer: off)
@@ -375,13 +459,17 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
     std::memset(&sum, 0, sizeof sum);
     int iters = 0;
     int64_t cs_bytes = 0;
-    if (fixed || (rc.rate_bpp <= 0.0 && !by_rates)) {
+    if (fixed || by_psnr || (rc.rate_bpp <= 0.0 && !by_rates)) {
         // lossless: per -flush_period stripe, layer l keeps the passes whose
         // slopes clear lossless_layer_frac(l) of the stripe's tier-1 bytes;
         // fixed slopes: layer l keeps the passes whose slopes clear the
         // caller's threshold, in every stripe (no target, no rate loop)
         for (int grow = 0;; grow++) {
-            if (!(fixed ? ctx->gpu.select_keys(plan, keys, err) : ctx->gpu.select_lossless(plan, err)) ||
+            // PSNR targets: layer l keeps the passes whose slopes clear the
+            // highest threshold that leaves at most qtarget[l] quanta
+            if (!(fixed     ? ctx->gpu.select_keys(plan, keys, err)
+                  : by_psnr ? ctx->gpu.select_psnr(plan, qtarget, err)
+                            : ctx->gpu.select_lossless(plan, err)) ||
                 !ctx->gpu.t2_size(plan, true, prof, st, sum, err))
                 return fail(err);
             if ((sum.err & kErrSlotPool) && grow < 2) {
@@ -394,8 +482,11 @@ int encode_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const jp2hip
             break;
         }
         if (sum.err) return fail("tier-1 output capacity exceeded");
-        iters = fixed ? 0 : 1;
+        iters = fixed || by_psnr ? 0 : 1;
         cs_bytes = (int64_t)mh_bytes + tlm + sum.part_bytes + 2;
+        // (targets that do not decrease cannot give thresholds that increase)
+        for (int l = 1; by_psnr && l < rc.layers; l++)
+            if (sum.kc[l] > sum.kc[l - 1]) return fail("layer psnr: the thresholds found increase with the layer");
     } else {
         // the rate loop runs on the device (GpuEncoder::rate_loop): one
         // iteration per host wait, what the usual encode needs (its first
@@ -498,8 +589,16 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // per-layer rates (collective, like the slopes): a lossless recipe's plan
     // then has one rate-control group, and takes the rate-driven exchange
     const bool by_rates = !ctx->rates.empty();
-    if (!build_plan(full, rc, up.width, up.height, enc_nc, enc_bits, err, by_rates && rc.rate_bpp <= 0.0))
+    // PSNR targets likewise (collective): one group, and an exchange of their own
+    const bool by_psnr = !ctx->psnr.empty();
+    if (!build_plan(full, rc, up.width, up.height, enc_nc, enc_bits, err, (by_rates || by_psnr) && rc.rate_bpp <= 0.0))
         return fail(err);
+    int64_t qtarget[kMaxLayers] = {};
+    if (by_psnr) {  // (the full plan's: the same on every rank)
+        if (!quanta_fit(full)) return fail("layer psnr: the distortion quanta of an image this large could overflow 63 bits");
+        layer_psnr_targets(full.w, full.h, full.nc, full.bits, ctx->psnr.data(), rc.layers, qtarget);
+    }
+    ctx->gpu.set_psnr(by_psnr ? full.bits : 0);
     int tr0, tr1;
     if (untiled(recipe)) {  // one tile row, all of it rank 0's (jp2hip_split_rows with tile_h = 0)
         tr0 = rank ? 1 : 0;
@@ -549,7 +648,7 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     // fixed-slope layers (collective, like the organisation): no target,
     // nothing predicted, no threshold exchange
     const bool fixed = !ctx->slopes.empty();
-    int64_t skip_target = fixed ? -1 : skip_target_of(rc, full.w, full.h, tlm + E);
+    int64_t skip_target = fixed || by_psnr ? -1 : skip_target_of(rc, full.w, full.h, tlm + E);
     int64_t ltarget[kMaxLayers] = {}, lbudget[kMaxLayers] = {};
     if (by_rates) {  // (as encode_core)
         layer_rate_targets(full, ctx->rates.data(), rc.layers, tlm + E, ltarget, lbudget);
@@ -631,6 +730,21 @@ int encode_split_core(jp2hip_ctx *ctx, const void *d_src, size_t src_len, const 
     for (int attempt = 0; attempt < 2; attempt++) {
         if (fixed) {
             K = slope_keys(ctx->slopes);
+            if (!round(false, true)) return fail(err);
+            iters = 0;
+            break;
+        }
+        if (by_psnr) {
+            // every rank's segments with their quanta; the thresholds agreed
+            // over the same all-reduce, then one round at those keys (a rank
+            // that failed still joins every exchange)
+            ok = ok && (!have || ctx->gpu.segments(sub, keys, cum, err, true));
+            std::vector<int64_t> flag(1);
+            if (!exchange(flag, 0, ok) || !ok) return fail(err);
+            if (jp2hip_split_psnr_thresholds(keys.data(), cum.data(), (int64_t)keys.size(), qtarget, L, sp, K.data()) != 0)
+                return fail("split: threshold exchange failed");
+            for (int l = 1; l < L; l++)
+                if (K[l] > K[l - 1]) return fail("layer psnr: the thresholds found increase with the layer");
             if (!round(false, true)) return fail(err);
             iters = 0;
             break;

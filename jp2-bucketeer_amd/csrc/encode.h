@@ -33,6 +33,21 @@ bool check_layer_slopes(const double *slopes, int n, const jp2hip_recipe *rc, st
 // top layer, no decrease) are refused; with rc also n other than rc->layers, a
 // last entry other than 0 under rate_bpp <= 0 and a 0 entry under rate_bpp > 0.
 bool check_layer_rates(const double *rates, int n, const jp2hip_recipe *rc, std::string &err);
+// jp2hip_set_layer_psnr's targets (dB) under the rules of the rates: a NaN, an
+// infinity, a negative value and a sequence that decreases (a last 0 is the
+// lossless top layer) are refused; with rc also n other than rc->layers, a last
+// entry other than 0 under rate_bpp <= 0 and a 0 entry under rate_bpp > 0.
+bool check_layer_psnr(const double *psnr_db, int n, const jp2hip_recipe *rc, std::string &err);
+// The quanta (psnr_quantum.h) each layer may leave in a width x height image
+// of `components` samples of `bits` bits a pixel: floor(peak^2 N 2^-s /
+// 10^(psnr / 10)), saturated at 2^62; a last entry of 0 (the lossless top
+// layer) gives -1.  The one conversion from dB every encode route uses.
+void layer_psnr_targets(int width, int height, int components, int bits, const double *psnr_db, int n,
+                        int64_t *targets);
+struct Plan;
+// Whether an encode of this plan by PSNR targets is accepted: an upper bound
+// on its hull segments' quanta (psnr_quantum.h) stays below 2^63.
+bool quanta_fit(const Plan &plan);
 // orient: the encode's source orientation, resolved (0 off, 1..8: TIFF
 // Orientation; never JP2HIP_ORIENT_TIFF -- the callers that parse a TIFF read
 // its tag, source_orientation())

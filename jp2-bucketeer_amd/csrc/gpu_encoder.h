@@ -55,7 +55,9 @@ struct FrontJob;  // front.hip
     /* the layer report's per-workgroup distortion sums and their totals (k_layer_dist) */                   \
     X(ldist)                                                                                                  \
     /* an encode by per-layer rates: kMaxLayers targets, then kMaxLayers first budgets (rates_load) */        \
-    X(ltarget)
+    X(ltarget)                                                                                                \
+    /* an encode by PSNR targets: k_hull's histogram of distortion quanta per slope bin */                   \
+    X(pcrd_hq)
 
 // Owns all device memory of a context; buffers only grow while the context
 // stays within its soft limit, so repeated encodes of the same geometry never
@@ -168,6 +170,15 @@ class GpuEncoder {
     // (and fixed-slope layers: the caller's own), the same keys for every
     // rate-control group, shown as K and as Kc (T2Summary::kc)
     bool select_keys(const Plan &plan, const std::vector<uint64_t> &K, std::string &err);
+    // quality layers by target PSNR (jp2hip_set_layer_psnr).  set_psnr before
+    // run_front: bits > 0 makes its k_hull also histogram every hull segment's
+    // distortion quantum for `bits`-bit samples (psnr_quantum.h) and the
+    // candidate lists 64 bits wide; 0 (every other encode): neither exists.
+    // select_psnr then finds, on the device, per layer the highest threshold
+    // that leaves at most target[l] quanta (-1: the lossless top layer) and
+    // applies it (enqueued only; t2_size reads the result, its kc the keys)
+    void set_psnr(int bits) { psnr_bits = bits; }
+    bool select_psnr(const Plan &plan, const int64_t *target, std::string &err);
     // jp2hip_layer_report's distortion: per layer, over the plan's blocks,
     // weight x the distortion decrease of the passes the final selection
     // (the thresholds in `thr`) leaves out; d[kMaxLayers]; one host wait
@@ -205,8 +216,10 @@ class GpuEncoder {
     // stage times of the last encode from its events (profile mode; call
     // after the encode's last host wait)
     bool collect_profile(StageTimes &st, std::string &err);
-    // this encode's hull segments: slope keys (descending) and inclusive byte sums
-    bool segments(const Plan &plan, std::vector<uint64_t> &keys, std::vector<int64_t> &cum, std::string &err);
+    // this encode's hull segments: slope keys (descending) and inclusive byte
+    // sums -- quanta: inclusive sums of distortion quanta (after set_psnr)
+    bool segments(const Plan &plan, std::vector<uint64_t> &keys, std::vector<int64_t> &cum, std::string &err,
+                  bool quanta = false);
     hipStream_t get_stream() const { return stream; }
     int get_device() const { return device; }
     // the stream and the main buffers are on this context's device (a
@@ -234,7 +247,7 @@ class GpuEncoder {
     bool front_dumps(const FrontJob &j, std::string &err);
     bool apply_thresholds(const Plan &plan, const int *halt, std::string &err);
     void select_launch(const Plan &plan, const int *halt, const RateState *init = nullptr, RateState *rs = nullptr,
-                       bool by_rates = false);
+                       bool by_rates = false, const int64_t *qtarget = nullptr);
     T2Args t2_args(const Plan &plan) const;
     // tier-2 sizing; with rs (device rate loop) k_t2_total also runs the
     // loop's step, leaving state + summary at out_rs (host-mapped)
@@ -312,6 +325,7 @@ class GpuEncoder {
     bool expand_timed = false;  // this encode recorded kEvExpandBegin / End
     bool orient_timed = false;  // ... kEvOrientBegin / End
     int nseg = 0;  // hull segments at most: the bound sum(3 Mb - 2)
+    int psnr_bits = 0;  // set_psnr: the sample depth of an encode by PSNR targets, 0 = any other encode
     std::vector<int64_t> h_hist;
     std::vector<uint64_t> strips_host;  // strip offsets last uploaded to `strips`
     const void *strips_dev = nullptr;

@@ -7,8 +7,10 @@
 // group (k_fill_keys: the tile-split's agreed keys and fixed-slope layers) and
 // the layer report's distortion sums (k_layer_dist, k_layer_dist_sum).  The
 // GpuEncoder members that launch them follow the kernels: hull_launch,
-// select_launch, select_lossless, select_keys, layer_dist, apply_thresholds,
-// rate_loop, segments.
+// select_launch, select_lossless, select_psnr, select_keys, layer_dist,
+// apply_thresholds, rate_loop, segments.  k_hull, k_select and
+// k_select_resolve have a second instantiation each for quality layers by
+// target PSNR, whose measure is distortion quanta (psnr_quantum.h), not bytes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,11 +18,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "device_common.h"
 #include "gpu_encoder.h"
 #include "hip_check.h"
+#include "psnr_quantum.h"
 #include "stage_repeat.h"
 
 namespace jp2hip {
@@ -53,6 +57,10 @@ struct HullArgs {
     const unsigned long long *acc;
     const uint8_t *pmin;
     T2Summary *sum;
+    // quality layers by target PSNR (k_hull<true> only): the same histogram of
+    // distortion quanta (psnr_quantum.h; zeroed by hull_launch) for `qbits`-bit samples
+    unsigned long long *hquanta;  // [group][kPcrdBins]
+    int qbits;
 };
 
 // slope-key bin: monotone in the key (positive doubles order like their bits)
@@ -70,7 +78,7 @@ struct HullPt {
 };
 static_assert(sizeof(HullPt) == 16, "HullPt layout");
 
-__device__ __forceinline__ void hull_one(const HullArgs &a, int b, uint32_t *lb, uint32_t *lc) {
+__device__ __forceinline__ int hull_one(const HullArgs &a, int b, uint32_t *lb, uint32_t *lc) {
     const int np = a.npasses[b];
     const int32_t *R = a.rates + (size_t)b * kMaxPasses;
     const int64_t *Dd = a.dists + (size_t)b * kMaxPasses;
@@ -155,17 +163,26 @@ __device__ __forceinline__ void hull_one(const HullArgs &a, int b, uint32_t *lb,
         }
     }
     a.nhull[b] = (uint8_t)nh;
+    return nh;
 }
 
+// Q: also the histogram of distortion quanta (an encode by PSNR targets).  It
+// is built from the finished hull, not on the push / pop path: a quantum is a
+// rounded product, which a pop could not take back out the way it takes bytes.
+// Each segment's quantum goes to the workgroup's 64-bit LDS bins (32 KB more;
+// only this instantiation has them), the bins to memory once per workgroup.
 constexpr int kHullThreads = 256;
+template <bool Q>
 __global__ void __launch_bounds__(kHullThreads) k_hull(HullArgs a) {
     // a workgroup's bytes per bin fit 32 bits (256 blocks of < 100 KB; the
     // pops' transient negatives wrap and cancel): 32 KB of LDS, not 48
     __shared__ uint32_t lb[kPcrdBins];
     __shared__ uint32_t lc[kPcrdBins];
+    __shared__ unsigned long long lq[Q ? kPcrdBins : 1];
     for (int i = threadIdx.x; i < kPcrdBins; i += kHullThreads) {
         lb[i] = 0;
         lc[i] = 0;
+        if (Q) lq[i] = 0ull;
     }
     __syncthreads();
     const int g = blockIdx.y, gb1 = a.grp_b0[g + 1];
@@ -174,7 +191,19 @@ __global__ void __launch_bounds__(kHullThreads) k_hull(HullArgs a) {
     int64_t tb = 0, tp = 0, nd = 0;
     bool sk = false;
     if (b < gb1) {
-        hull_one(a, b, lb, lc);
+        const int nh = hull_one(a, b, lb, lc);
+        if (Q) {
+            const uint64_t *hk = a.hkey + (size_t)b * (kMaxPasses + 1);
+            const HullPt *hs = (const HullPt *)a.hdist + (size_t)b * (kMaxPasses + 1);
+            const double wgt = a.weight[b];
+            int64_t prev = 0;
+            for (int i = 1; i < nh; i++) {  // (the lane reads back its own stores)
+                const int64_t d = hs[i].d;
+                const int64_t q = distortion_quantum(wgt, d - prev, a.qbits);
+                prev = d;
+                if (q) atomicAdd(&lq[pcrd_bin(hk[i])], (unsigned long long)q);
+            }
+        }
         tb = a.lengths[b];
         tp = a.npasses[b];
         nd = (int64_t)(a.acc[b] & ((1ull << 40) - 1ull));  // decisions (k_t1_cm3)
@@ -196,6 +225,7 @@ __global__ void __launch_bounds__(kHullThreads) k_hull(HullArgs a) {
         if (lc[i]) {
             atomicAdd(&a.hbytes[(size_t)g * kPcrdBins + i], (unsigned long long)lb[i]);
             atomicAdd(&a.hcount[(size_t)g * kPcrdBins + i], lc[i]);
+            if (Q && lq[i]) atomicAdd(&a.hquanta[(size_t)g * kPcrdBins + i], lq[i]);
         }
 }
 
@@ -252,7 +282,18 @@ struct SelectArgs {
     uint32_t *ctl;    // [group][1 + i] fill of list i ([0] unused)
     uint64_t *K, *Kc;
     int64_t *dbg;     // debug builds: [0] lists, [1 + i] list sizes, [33 + l] rounds, [65 + l] survivors
+    // The distortion instantiations (D; an encode by PSNR targets): hbytes is
+    // the histogram of quanta, a candidate's size its quantum (64 bits, lsize64)
+    // from the hull's cumulative distortions and the block's weight, and layer
+    // l may leave qtarget[l] quanta (-1: a lossless top layer, K = 0)
+    int64_t qtarget[kMaxLayers];
+    uint64_t *lsize64;
+    const int64_t *hdist;
+    const double *weight;
+    int qbits;
 };
+// lneed of a layer that takes nothing (D): its threshold is one above the largest key
+constexpr int64_t kSelNothing = INT64_MIN;
 
 // 256 threads a workgroup (4 waves): under load a 1 024-thread workgroup
 // waits for 16 free wave slots on one CU
@@ -271,11 +312,23 @@ struct SelBins {
     int list_bin[kMaxLayers];
     uint32_t list_off[kMaxLayers + 1];
     int nlist;
+    int wtop[kSelThreads / 64];         // D: each wave's highest bin that holds a segment (-1: none)
 };
 // The suffix sums are kept per thread chunk (kSelPer bins), 2 KB of LDS
 // instead of a 32 KB table per bin (and no 4 KB bin -> list map): a layer's
 // bin is found by a binary search over the chunks, then a walk down its
 // chunk's bins (re-read from L2).
+//
+// D (distortion): the measure is quanta and layer l must remove need = total -
+// qtarget[l] of them.  With T = need - 1 the search below is the byte select's
+// unchanged -- the largest v whose suffix sum exceeds T is the largest whose
+// suffix sum reaches need -- but v itself is the threshold (its tie group is
+// taken), where the byte select's v is the first key not taken.  need <= 0
+// takes nothing: the threshold is the byte select's for a budget of 0, one
+// above the largest key of all (kSelNothing; the bin is the highest that holds
+// a segment, found from the counts, since a segment may have no quanta).  A
+// need the total does not reach (qtarget -1) takes every segment, K = 0.
+template <bool D>
 __device__ __forceinline__ void select_bins(const SelectArgs &a, SelBins &sh, int g) {
     const int tid = threadIdx.x, L = a.layers;
     const unsigned long long *hbytes = a.hbytes + (size_t)g * kPcrdBins;
@@ -292,17 +345,37 @@ __device__ __forceinline__ void select_bins(const SelectArgs &a, SelBins &sh, in
         const uint64_t pre = wg_excl_scan64<kSelThreads>(s, sh.wsum, tot);
         csfx[tid] = tot - pre;
         if (tid == 0) csfx[kSelThreads] = 0;
+        if (D) {
+            int top = -1;
+#pragma unroll
+            for (int i = 0; i < kSelPer; i++) top = hcount[kSelPer * tid + i] ? kSelPer * tid + i : top;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) top = max(top, __shfl_xor(top, o, 64));
+            if ((tid & 63) == 0) sh.wtop[tid >> 6] = top;
+        }
     }
     __syncthreads();
     if (tid < L) {
-        // (a negative budget takes nothing, as 0 does: every segment has bytes)
-        const int64_t B = a.init_on == 1 ? (a.init.budget < 0 ? 0 : a.init.budget) >> (L - 1 - tid)
-                          : a.lossless ? (int64_t)((a.gtot[g] * (unsigned long long)a.frac[tid]) >> 16)
-                                       : a.budget[(size_t)g * kMaxLayers + tid];
-        const int64_t T = B < 0 ? 0 : B;
+        int64_t T;
+        bool nothing = false;
+        if (D) {
+            const int64_t total = (int64_t)csfx[0], tgt = a.qtarget[tid];
+            const int64_t need = tgt < 0 ? total + 1 : total - tgt;
+            nothing = need <= 0;
+            T = need - 1;
+        } else {
+            // (a negative budget takes nothing, as 0 does: every segment has bytes)
+            const int64_t B = a.init_on == 1 ? (a.init.budget < 0 ? 0 : a.init.budget) >> (L - 1 - tid)
+                              : a.lossless ? (int64_t)((a.gtot[g] * (unsigned long long)a.frac[tid]) >> 16)
+                                           : a.budget[(size_t)g * kMaxLayers + tid];
+            T = B < 0 ? 0 : B;
+        }
         int b = -1;
         int64_t above = 0;  // S(b + 1)
-        if ((int64_t)csfx[0] > T) {
+        if (D && nothing) {
+#pragma unroll
+            for (int w = 0; w < kSelThreads / 64; w++) b = max(b, sh.wtop[w]);
+        } else if ((int64_t)csfx[0] > T) {
             // the largest chunk whose suffix sum exceeds T ...
             int lo = 0, hi = kSelThreads - 1;
             while (lo < hi) {
@@ -323,7 +396,7 @@ __device__ __forceinline__ void select_bins(const SelectArgs &a, SelBins &sh, in
             above = (int64_t)S;
         }
         lbin[tid] = b;
-        lneed[tid] = b < 0 ? 0 : T - above;
+        lneed[tid] = b < 0 ? 0 : (D && nothing) ? kSelNothing : T - above;
     }
     __syncthreads();
     if (tid == 0) {  // one candidate list per distinct bin
@@ -347,6 +420,7 @@ __device__ __forceinline__ void select_bins(const SelectArgs &a, SelBins &sh, in
     __syncthreads();
 }
 
+template <bool D>
 __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
     __shared__ SelBins sh;
     const int tid = threadIdx.x, lane = tid & 63, g = blockIdx.y;
@@ -366,7 +440,7 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
             for (int l = 0; l < a.layers; l++) a.budget_w[l] = a.budget[l];
     }
     if (gb0 + (int)blockIdx.x * kSelThreads >= gb1) return;  // (the whole workgroup)
-    select_bins(a, sh, g);
+    select_bins<D>(a, sh, g);
     const uint32_t *list_off = sh.list_off;
     const int *list_bin = sh.list_bin;
     const int nlist = sh.nlist;
@@ -406,7 +480,13 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
                             const uint32_t at =
                                 seg0 + list_off[lj] + base + (uint32_t)__popcll(grp & ((1ull << lane) - 1ull));
                             a.lkey[at] = key;
-                            a.lsize[at] = (uint32_t)(R[hp[i] - 1] - (hp[i - 1] ? R[hp[i - 1] - 1] : 0));
+                            if (D) {
+                                const HullPt *hs = (const HullPt *)a.hdist + (size_t)b * (kMaxPasses + 1);
+                                a.lsize64[at] = (uint64_t)distortion_quantum(
+                                    a.weight[b], hs[i].d - (i > 1 ? hs[i - 1].d : 0), a.qbits);
+                            } else {
+                                a.lsize[at] = (uint32_t)(R[hp[i] - 1] - (hp[i - 1] ? R[hp[i - 1] - 1] : 0));
+                            }
                         }
                         todo &= ~grp;
                     }
@@ -424,19 +504,24 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
 // pair took 104.5 us alone instead of 53 + 23 with the layers in turn, and
 // 116.9 with a wave per layer, 4x longer candidate walks per wave; the C2
 // bench did not move: profiles/r05/ab_select_fold.txt.)
+// D: the sizes are quanta (64 bits), the threshold is v itself, and a layer
+// that takes nothing (kSelNothing) gets one above its list's largest key.
+template <bool D>
 __global__ void __launch_bounds__(kSelThreads) k_select_resolve(SelectArgs a) {
+    using SizeT = typename std::conditional<D, uint64_t, uint32_t>::type;
+    const SizeT *lsize = D ? (const SizeT *)a.lsize64 : (const SizeT *)a.lsize;
     __shared__ SelBins sh;
     // the narrowing state and the survivors
     __shared__ uint64_t rlo, rhi, rmax;
     __shared__ int64_t rneed;
     __shared__ uint32_t rcount;
     __shared__ uint64_t bkey[kSelBrute];
-    __shared__ uint32_t bsize[kSelBrute];
+    __shared__ SizeT bsize[kSelBrute];
     __shared__ uint64_t hist[kResBins];
     __shared__ uint32_t hcnt[kResBins];
     const int tid = threadIdx.x, lane = tid & 63, l = blockIdx.x, g = blockIdx.y;
     if (a.halt && *a.halt) return;  // (k_select has reset it on a first iteration)
-    select_bins(a, sh, g);
+    select_bins<D>(a, sh, g);
     uint64_t *wsum = sh.wsum;
     const int *lbin = sh.lbin, *lli = sh.lli;
     const int64_t *lneed = sh.lneed;
@@ -465,7 +550,7 @@ __global__ void __launch_bounds__(kSelThreads) k_select_resolve(SelectArgs a) {
         if (tid == 0) {
             rcount = i1 - i0;
             rneed = lneed[l];
-            if (bn > 0 && bn < kPcrdBins - 1) {
+            if (bn > 0 && bn < kPcrdBins - 1 && !(D && lneed[l] == kSelNothing)) {
                 rlo = (uint64_t)(bn + kPcrdBinBase) << 47;
                 rhi = rlo + ((1ull << 47) - 1ull);
             } else {  // a clamped end bin: the candidates' own key range
@@ -492,6 +577,10 @@ __global__ void __launch_bounds__(kSelThreads) k_select_resolve(SelectArgs a) {
             }
             __syncthreads();
         }
+        if (D && lneed[l] == kSelNothing) {  // (rhi: the largest key of the highest bin that holds a segment)
+            if (tid == 0) Kg[l] = Kcg[l] = rhi + 1;
+            return;
+        }
         for (int round = 0;; round++) {
             const uint64_t flo = rlo, fhi = rhi;
             const uint32_t cnt = rcount;
@@ -511,7 +600,7 @@ __global__ void __launch_bounds__(kSelThreads) k_select_resolve(SelectArgs a) {
                         if (k >= flo && k <= fhi) {
                             const uint32_t at = atomicAdd(&rcount, 1u);
                             bkey[at] = k;  // (cnt <= kSelBrute candidates lie in range)
-                            bsize[at] = a.lsize[i];
+                            bsize[at] = lsize[i];
                         }
                     }
                     __syncthreads();
@@ -525,7 +614,7 @@ __global__ void __launch_bounds__(kSelThreads) k_select_resolve(SelectArgs a) {
                 }
                 __syncthreads();
                 if (tid == 0) {
-                    Kg[l] = Kcg[l] = rmax + 1;
+                    Kg[l] = Kcg[l] = D ? rmax : rmax + 1;
                     if (a.dbg && g == 0) {
                         a.dbg[33 + l] = round;
                         a.dbg[65 + l] = cnt;
@@ -545,7 +634,7 @@ __global__ void __launch_bounds__(kSelThreads) k_select_resolve(SelectArgs a) {
                 const uint64_t k = a.lkey[i];
                 if (k >= flo && k <= fhi) {
                     const uint32_t sb = (uint32_t)((k - flo) >> shift);
-                    atomicAdd((unsigned long long *)&hist[sb], (unsigned long long)a.lsize[i]);
+                    atomicAdd((unsigned long long *)&hist[sb], (unsigned long long)lsize[i]);
                     atomicAdd(&hcnt[sb], 1u);
                 }
             }
@@ -636,7 +725,8 @@ __global__ void __launch_bounds__(kSegThreads) k_seg_offsets(int nblocks, const 
 // (up to the bound `nbound`) get key 0 and size 0
 __global__ void __launch_bounds__(256) k_seg_emit(int nblocks, const uint8_t *nhull, const uint8_t *hpass,
                                                   const uint64_t *hkey, const int32_t *rates,
-                                                  const int32_t *segoff, uint64_t *keys, int64_t *vals) {
+                                                  const int32_t *segoff, uint64_t *keys, int64_t *vals,
+                                                  const int64_t *hdist, const double *weight, int qbits) {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nblocks) return;
     int nh = nhull[b];
@@ -646,7 +736,12 @@ __global__ void __launch_bounds__(256) k_seg_emit(int nblocks, const uint8_t *nh
     int o = segoff[b];
     for (int i = 1; i < nh; i++) {
         keys[o + i - 1] = hk[i];
-        vals[o + i - 1] = (int64_t)(R[hp[i] - 1] - (hp[i - 1] ? R[hp[i - 1] - 1] : 0));
+        if (qbits) {  // by PSNR targets: the segment's quantum, not its bytes
+            const HullPt *hs = (const HullPt *)hdist + (size_t)b * (kMaxPasses + 1);
+            vals[o + i - 1] = distortion_quantum(weight[b], hs[i].d - (i > 1 ? hs[i - 1].d : 0), qbits);
+        } else {
+            vals[o + i - 1] = (int64_t)(R[hp[i] - 1] - (hp[i - 1] ? R[hp[i - 1] - 1] : 0));
+        }
     }
 }
 
@@ -797,14 +892,33 @@ bool GpuEncoder::hull_launch(const Plan &plan, std::string &err) {
     ha.sum = (T2Summary *)t2sum.ptr;
     ha.grp_b0 = (const int32_t *)grptab.ptr;
     ha.gtot = (unsigned long long *)gtot.ptr;
-    REPEAT_IF(4) if (nb) hipLaunchKernelGGL(k_hull, dim3((grp_max_blocks(plan) + kHullThreads - 1) / kHullThreads, G),
-                                            dim3(kHullThreads), 0, stream, ha);
+    ha.hquanta = nullptr;
+    ha.qbits = psnr_bits;
+    const dim3 grid((grp_max_blocks(plan) + kHullThreads - 1) / kHullThreads, G);
+    if (psnr_bits) {
+        // an encode by PSNR targets: the histogram of quanta beside the bytes'
+        // (a buffer no other encode allocates), zeroed here in stream order
+        if (!ensure<unsigned long long>(pcrd_hq, (size_t)std::max(G, 1) * kPcrdBins, err)) return false;
+        HIPCHECK(hipMemsetAsync(pcrd_hq.ptr, 0, (size_t)std::max(G, 1) * kPcrdBins * sizeof(unsigned long long), stream));
+        ha.hquanta = (unsigned long long *)pcrd_hq.ptr;
+        // (no REPEAT_IF: the stage-repeat builds time the benchmark's path,
+        // and a repeat would add every quantum again -- the histogram is
+        // zeroed above, not by k_quant as the bytes' is.  A tile-split rank
+        // builds the histogram too although only segments() reads quanta on
+        // that route: one launch argument serves both routes)
+        if (nb) hipLaunchKernelGGL(k_hull<true>, grid, dim3(kHullThreads), 0, stream, ha);
+    } else {
+        REPEAT_IF(4) if (nb) hipLaunchKernelGGL(k_hull<false>, grid, dim3(kHullThreads), 0, stream, ha);
+    }
     HIPCHECK(hipGetLastError());
     // candidate lists: room for every hull segment (the bound sum(3 Mb - 2))
     int64_t nseg_bound = 0;
     for (int i = 0; i < nb; i++) nseg_bound += std::max(0, 3 * (int)plan.blocks[i].Mb - 2);
     nseg = (int)nseg_bound;
-    return ensure<uint64_t>(sel_key, std::max(nseg, 1), err) && ensure<uint32_t>(sel_size, std::max(nseg, 1), err) &&
+    // (by PSNR targets a candidate's size is its quantum: 64 bits)
+    return ensure<uint64_t>(sel_key, std::max(nseg, 1), err) &&
+           (psnr_bits ? ensure<uint64_t>(sel_size, std::max(nseg, 1), err)
+                      : ensure<uint32_t>(sel_size, std::max(nseg, 1), err)) &&
            ensure<uint64_t>(thr, 2 * (size_t)G * kMaxLayers, err);
 }
 
@@ -812,7 +926,7 @@ bool GpuEncoder::hull_launch(const Plan &plan, std::string &err) {
 // bytes, else from `budget` (the device rate loop's) -- thresholds of group g
 // -> thr[g * kMaxLayers ..), Kc -> thr[(G + g) * kMaxLayers ..)
 void GpuEncoder::select_launch(const Plan &plan, const int *halt, const RateState *init, RateState *rs,
-                               bool by_rates) {
+                               bool by_rates, const int64_t *qtarget) {
     const int nb = (int)plan.blocks.size(), G = plan.ngroups();
     if (!nb) return;
     SelectArgs sa;
@@ -850,9 +964,23 @@ void GpuEncoder::select_launch(const Plan &plan, const int *halt, const RateStat
         if (ensure<int64_t>(dbgsel, 128, e)) sa.dbg = (int64_t *)dbgsel.ptr;
     }
 #endif
-    hipLaunchKernelGGL(k_select, dim3((grp_max_blocks(plan) + kSelThreads - 1) / kSelThreads, G), dim3(kSelThreads), 0,
-                       stream, sa);
-    hipLaunchKernelGGL(k_select_resolve, dim3(plan.rc.layers, G), dim3(kSelThreads), 0, stream, sa);
+    const dim3 grid((grp_max_blocks(plan) + kSelThreads - 1) / kSelThreads, G);
+    if (qtarget) {
+        // by PSNR targets: the distortion instantiations over the histogram of
+        // quanta; no budgets, no loop state
+        sa.hbytes = (const unsigned long long *)pcrd_hq.ptr;
+        sa.lossless = 0;
+        std::memcpy(sa.qtarget, qtarget, sizeof(int64_t) * plan.rc.layers);
+        sa.lsize64 = (uint64_t *)sel_size.ptr;
+        sa.hdist = (const int64_t *)hdist.ptr;
+        sa.weight = (const double *)weight.ptr;
+        sa.qbits = psnr_bits;
+        hipLaunchKernelGGL(k_select<true>, grid, dim3(kSelThreads), 0, stream, sa);
+        hipLaunchKernelGGL(k_select_resolve<true>, dim3(plan.rc.layers, G), dim3(kSelThreads), 0, stream, sa);
+        return;
+    }
+    hipLaunchKernelGGL(k_select<false>, grid, dim3(kSelThreads), 0, stream, sa);
+    hipLaunchKernelGGL(k_select_resolve<false>, dim3(plan.rc.layers, G), dim3(kSelThreads), 0, stream, sa);
 }
 
 // lossless "-rate -": each -flush_period stripe (rate-control group) keeps
@@ -862,6 +990,21 @@ bool GpuEncoder::select_lossless(const Plan &plan, std::string &err) {
     HIPCHECK(hipSetDevice(device));
     HIPCHECK(hipEventRecord(ev[kEvSelectBegin], stream));
     select_launch(plan, nullptr);
+    HIPCHECK(hipGetLastError());
+    return apply_thresholds(plan, nullptr, err);
+}
+
+// by PSNR targets (jp2hip_set_layer_psnr): per layer the highest threshold
+// that leaves at most target[l] quanta (layer_psnr_targets); what follows is
+// the fixed-slope encode at those keys (k_apply, tier-2, the report)
+bool GpuEncoder::select_psnr(const Plan &plan, const int64_t *target, std::string &err) {
+    HIPCHECK(hipSetDevice(device));
+    if (!psnr_bits || !pcrd_hq.ptr) {
+        err = "select_psnr: the hulls were built without the histogram of quanta";
+        return false;
+    }
+    HIPCHECK(hipEventRecord(ev[kEvSelectBegin], stream));
+    select_launch(plan, nullptr, nullptr, nullptr, false, target);
     HIPCHECK(hipGetLastError());
     return apply_thresholds(plan, nullptr, err);
 }
@@ -995,7 +1138,7 @@ bool GpuEncoder::rate_loop(const Plan &plan, const RateState &init, bool restart
 }
 
 bool GpuEncoder::segments(const Plan &plan, std::vector<uint64_t> &keys, std::vector<int64_t> &cum,
-                          std::string &err) {
+                          std::string &err, bool quanta) {
     HIPCHECK(hipSetDevice(device));
     // every hull segment (key, bytes), listed on the device, sorted here by
     // key, descending (the tile-split exchange's input; the single-image path
@@ -1011,7 +1154,8 @@ bool GpuEncoder::segments(const Plan &plan, std::vector<uint64_t> &keys, std::ve
                        (int32_t *)segcnt.ptr, (int32_t *)segoff.ptr);
     hipLaunchKernelGGL(k_seg_emit, dim3((nb + 255) / 256), dim3(256), 0, stream, nb, (const uint8_t *)nhull.ptr,
                        (const uint8_t *)hpass.ptr, (const uint64_t *)hkey.ptr, (const int32_t *)rates.ptr,
-                       (const int32_t *)segoff.ptr, (uint64_t *)segkey.ptr, (int64_t *)segval.ptr);
+                       (const int32_t *)segoff.ptr, (uint64_t *)segkey.ptr, (int64_t *)segval.ptr,
+                       (const int64_t *)hdist.ptr, (const double *)weight.ptr, quanta ? psnr_bits : 0);
     HIPCHECK(hipGetLastError());
     int32_t *tail = (int32_t *)(h_tot + 5);  // pinned
     tail[0] = tail[1] = 0;

@@ -84,4 +84,59 @@ int jp2hip_split_thresholds(const uint64_t *keys, const int64_t *cum, int64_t ns
     return 0;
 }
 
+// The distortion counterpart (quality layers by target PSNR; pcrd.hip
+// k_select<true> has the single-image rule).  The inclusive sums are of
+// distortion quanta, and layer l must remove need[l] = total - targets[l] of
+// them, the total being the all-reduced sum of every rank's last entry.  With
+// S(k) = quanta of the segments whose key >= k (non-increasing),
+//     K[l] = max { k : S(k) >= need[l] },
+// the tie group at K[l] taken; found by the same bisection, the other way
+// round: lo keeps S(lo) >= need, hi keeps S(hi) < need.  A need the total does
+// not reach (targets[l] < 0, the lossless top layer) leaves lo at 0: every
+// segment.  need <= 0 takes nothing: the threshold is one above the largest
+// key of all ranks, which the same bisection finds over segment counts (the
+// largest k that one segment still reaches), and 0 when no rank has a segment.
+int jp2hip_split_psnr_thresholds(const uint64_t *keys, const int64_t *cum_quanta, int64_t nseg, const int64_t *targets,
+                                 int32_t layers, const jp2hip_split *split, uint64_t *K) {
+    if (layers <= 0 || layers > 64 || !targets || !K || nseg < 0 || (nseg > 0 && (!keys || !cum_quanta))) return -1;
+    const bool shared = split && split->world > 1;
+    auto reduce = [&](int64_t *v, int n) {
+        return !shared || (split->allreduce_sum && split->allreduce_sum(split->user, v, n) == 0);
+    };
+    int64_t tot[2] = {nseg ? cum_quanta[nseg - 1] : 0, nseg};  // quanta, segments
+    if (!reduce(tot, 2)) return -2;
+    const uint64_t kNone = 0x7FF0000000000001ull;  // (as jp2hip_split_thresholds)
+    std::vector<uint64_t> lo((size_t)layers, 0), hi((size_t)layers, kNone);
+    std::vector<int64_t> need((size_t)layers), v((size_t)layers);
+    std::vector<char> nothing((size_t)layers);
+    // this rank's segments with key >= k (keys descending)
+    auto count_at_least = [&](uint64_t k) {
+        return (int64_t)(std::upper_bound(keys, keys + nseg, k, [](uint64_t a, uint64_t b) { return a > b; }) - keys);
+    };
+    for (int l = 0; l < layers; l++) {
+        need[l] = targets[l] < 0 ? tot[0] + 1 : tot[0] - targets[l];
+        nothing[l] = need[l] <= 0;
+        if (nothing[l]) need[l] = 1;  // (of the counts: one segment)
+    }
+    for (;;) {
+        bool open = false;
+        for (int l = 0; l < layers; l++) {
+            const bool o = hi[l] - lo[l] > 1;
+            const uint64_t mid = lo[l] + ((hi[l] - lo[l]) >> 1);
+            v[l] = !o ? 0 : nothing[l] ? count_at_least(mid) : bytes_at_least(keys, cum_quanta, nseg, mid);
+            open = open || o;
+        }
+        if (!open) break;  // identical on every rank: same sums, same bounds
+        if (!reduce(v.data(), layers)) return -2;
+        for (int l = 0; l < layers; l++) {
+            if (hi[l] - lo[l] <= 1) continue;
+            const uint64_t mid = lo[l] + ((hi[l] - lo[l]) >> 1);
+            if (v[l] >= need[l]) lo[l] = mid;
+            else hi[l] = mid;
+        }
+    }
+    for (int l = 0; l < layers; l++) K[l] = nothing[l] ? (tot[1] ? lo[l] + 1 : 0) : lo[l];
+    return 0;
+}
+
 }  // extern "C"

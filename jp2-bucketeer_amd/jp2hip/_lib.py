@@ -166,6 +166,10 @@ EXPORTS = ("jp2hip_version", "jp2hip_last_error", "jp2hip_probe", "jp2hip_device
            # explicit per-layer rates (api.cpp, batch.cpp; the check, the step and the targets host only)
            "jp2hip_set_layer_rates", "jp2hip_batch_set_layer_rates", "jp2hip_check_layer_rates",
            "jp2hip_layer_rate_step", "jp2hip_layer_rate_targets",
+           # quality layers by target PSNR (api.cpp, batch.cpp, split.cpp; all but the two setters host only)
+           "jp2hip_set_layer_psnr", "jp2hip_batch_set_layer_psnr", "jp2hip_check_layer_psnr",
+           "jp2hip_distortion_quantum", "jp2hip_layer_psnr_targets", "jp2hip_split_psnr_thresholds",
+           "jp2hip_layer_psnr_fits",
            # source orientation, TIFF tag 274 (api.cpp, batch.cpp; the tag reader, the size and the rows host only)
            "jp2hip_set_source_orientation", "jp2hip_batch_set_source_orientation", "jp2hip_tiff_orientation",
            "jp2hip_oriented_size", "jp2hip_orientation_source_rows",
@@ -254,6 +258,17 @@ def lib():
     L.jp2hip_layer_rate_targets.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(Recipe), c_int32, c_int32,
                                             POINTER(c_double), c_int32, POINTER(c_int64), POINTER(c_int64),
                                             POINTER(c_int64)]
+    L.jp2hip_set_layer_psnr.argtypes = [c_void_p, POINTER(c_double), c_int32]
+    L.jp2hip_batch_set_layer_psnr.argtypes = [c_void_p, POINTER(c_double), c_int32]
+    L.jp2hip_check_layer_psnr.argtypes = [POINTER(c_double), c_int32, POINTER(Recipe)]
+    L.jp2hip_distortion_quantum.argtypes = [c_double, c_int64, c_int32]
+    L.jp2hip_distortion_quantum.restype = c_int64
+    L.jp2hip_layer_psnr_targets.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(c_double), c_int32,
+                                            POINTER(c_int64)]
+    L.jp2hip_layer_psnr_fits.argtypes = [c_int32, c_int32, c_int32, c_int32, POINTER(Recipe)]
+    L.jp2hip_split_psnr_thresholds.argtypes = [POINTER(c_uint64), POINTER(c_int64), c_int64,
+                                               POINTER(c_int64), c_int32, POINTER(Split),
+                                               POINTER(c_uint64)]
     L.jp2hip_slope_from_log2.argtypes = [c_double, c_int32]
     L.jp2hip_slope_from_log2.restype = c_double
     L.jp2hip_slope_to_log2.argtypes = [c_double, c_int32]
@@ -416,6 +431,46 @@ def check_layer_slopes(slopes, rcp: Recipe | None = None) -> None:
     arr, n = slopes_array(slopes)
     if lib().jp2hip_check_layer_slopes(arr, n, byref(rcp) if rcp is not None else None) != 0:
         raise Jp2hipError(last_error())
+
+
+def check_layer_psnr(psnr_db, rcp: Recipe | None = None) -> None:
+    """jp2hip_check_layer_psnr (no GPU): raises Jp2hipError, naming the entry,
+    for targets jp2hip_set_layer_psnr -- or, with ``rcp``, an encode of that
+    recipe -- refuses."""
+    arr, n = slopes_array(psnr_db)
+    if lib().jp2hip_check_layer_psnr(arr, n, byref(rcp) if rcp is not None else None) != 0:
+        raise Jp2hipError(last_error())
+
+
+def distortion_quantum(weight: float, dd: int, bits: int) -> int:
+    """jp2hip_distortion_quantum (no GPU): the integer one hull segment of
+    distortion decrease ``dd`` in a block of PCRD weight ``weight`` adds to a
+    selection by PSNR targets, for ``bits``-bit samples."""
+    q = int(lib().jp2hip_distortion_quantum(weight, dd, bits))
+    if q < 0:  # (quanta are never negative: the library's refusal of `bits`)
+        raise Jp2hipError(last_error())
+    return q
+
+
+def layer_psnr_fits(width: int, height: int, components: int, bits: int, rcp: Recipe) -> bool:
+    """jp2hip_layer_psnr_fits (no GPU): whether an encode of this image and
+    recipe by PSNR targets is accepted -- False when its distortion quanta
+    could overflow 63 bits.  Raises for a geometry or recipe no encode takes."""
+    r = lib().jp2hip_layer_psnr_fits(width, height, components, bits, byref(rcp))
+    if r < 0:
+        raise Jp2hipError(last_error())
+    return bool(r)
+
+
+def layer_psnr_targets(width: int, height: int, components: int, bits: int, psnr_db) -> list[int]:
+    """jp2hip_layer_psnr_targets (no GPU): the quanta each layer may leave in
+    an image of this size for ``psnr_db`` (layer 0 first); -1 for a last 0, the
+    lossless top layer."""
+    arr, n = slopes_array(psnr_db)
+    t = (c_int64 * 32)()
+    if lib().jp2hip_layer_psnr_targets(width, height, components, bits, arr, n, t) != 0:
+        raise Jp2hipError(last_error())
+    return [int(x) for x in t[:n]]
 
 
 def check_layer_rates(rates, rcp: Recipe | None = None) -> None:
@@ -669,6 +724,20 @@ class Encoder:
         fixed slopes off.  Not while the context is encoding."""
         arr, n = slopes_array(slopes)
         if lib().jp2hip_set_layer_slopes(self._h, arr, n) != 0:
+            raise Jp2hipError(last_error())
+
+    def set_layer_psnr(self, psnr_db=None):
+        """jp2hip_set_layer_psnr, for every later encode on this context and
+        its tile-split peers: layer l is the smallest selection whose predicted
+        PSNR is at least ``psnr_db[l]`` dB (OpenJPEG's ``-q``), layer 0 first
+        and none decreasing.  With ``Recipe.rate_bpp <= 0`` the last entry
+        must be 0: the top layer takes every coded pass.  There is no byte
+        target and no rate loop; ``layer_report().threshold`` holds the slopes
+        the layers were cut at.  None or () turns the targets off; targets,
+        rates and fixed slopes exclude one another.  Not while the context is
+        encoding."""
+        arr, n = slopes_array(psnr_db)
+        if lib().jp2hip_set_layer_psnr(self._h, arr, n) != 0:
             raise Jp2hipError(last_error())
 
     def set_layer_rates(self, rates=None):

@@ -65,7 +65,8 @@ UPLOAD_FN = CFUNCTYPE(c_int, c_void_p, c_char_p, c_char_p)
 BATCH_EXPORTS = ("jp2hip_batch_create", "jp2hip_batch_submit", "jp2hip_batch_wait",
                  "jp2hip_batch_pending", "jp2hip_batch_destroy", "jp2hip_batch_set_organisation",
                  "jp2hip_batch_set_tile_part_divisions", "jp2hip_batch_set_layer_slopes",
-                 "jp2hip_batch_set_layer_rates", "jp2hip_batch_set_source_orientation")
+                 "jp2hip_batch_set_layer_rates", "jp2hip_batch_set_layer_psnr",
+                 "jp2hip_batch_set_source_orientation")
 
 
 def _bind():
@@ -218,7 +219,7 @@ class BatchQueue:
     def __init__(self, device: int = 0, contexts: int = 12, reader_threads: int = 4,
                  uploader_threads: int = 4, host_threads: int = 0, delete_after_upload: bool = True,
                  write_output: bool = True, upload=None, tlm: bool = False, layer_slopes=None,
-                 layer_rates=None, orientation: int = _lib.ORIENT_OFF):
+                 layer_rates=None, orientation: int = _lib.ORIENT_OFF, layer_psnr=None):
         # one HW queue per context (+4 for the runtime); only takes effect if
         # nothing in this process has initialised HIP yet
         os.environ.setdefault("GPU_MAX_HW_QUEUES", str(max(4, min(32, (contexts or 12) + 4))))
@@ -244,6 +245,8 @@ class BatchQueue:
             self.set_layer_slopes(layer_slopes)
         if layer_rates is not None:  # explicit per-layer rates likewise
             self.set_layer_rates(layer_rates)
+        if layer_psnr is not None:  # PSNR targets likewise
+            self.set_layer_psnr(layer_psnr)
         if orientation != _lib.ORIENT_OFF:  # the source orientation likewise
             self.set_source_orientation(orientation)
 
@@ -265,6 +268,13 @@ class BatchQueue:
         context of the queue; only before the first submit."""
         arr, n = _lib.slopes_array(slopes)
         if _bind().jp2hip_batch_set_layer_slopes(self._h, arr, n) != 0:
+            raise _lib.Jp2hipError(_lib.last_error() or "the queue has taken a job already")
+
+    def set_layer_psnr(self, psnr_db=None):
+        """jp2hip_batch_set_layer_psnr: Encoder.set_layer_psnr on every
+        context of the queue; only before the first submit."""
+        arr, n = _lib.slopes_array(psnr_db)
+        if _bind().jp2hip_batch_set_layer_psnr(self._h, arr, n) != 0:
             raise _lib.Jp2hipError(_lib.last_error() or "the queue has taken a job already")
 
     def set_layer_rates(self, rates=None):

@@ -146,6 +146,29 @@ def thresholds(keys, cum, budgets, group: _Group | None = None) -> np.ndarray:
     return K
 
 
+def psnr_thresholds(keys, cum_quanta, targets, group: _Group | None = None) -> np.ndarray:
+    """Global layer thresholds of an encode by PSNR targets:
+    K[l] = max{k : sum over ranks of quanta with key >= k >= total - targets[l]}.
+
+    ``keys`` are this rank's hull-segment slope keys in descending order,
+    ``cum_quanta`` their inclusive running sums of distortion quanta and
+    ``targets`` what ``jp2hip.layer_psnr_targets`` gives (csrc/split.cpp)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    cum = np.ascontiguousarray(cum_quanta, dtype=np.int64)
+    targets = np.ascontiguousarray(targets, dtype=np.int64)
+    if keys.shape != cum.shape:
+        raise ValueError("keys and cum_quanta differ in length")
+    K = np.zeros(len(targets), dtype=np.uint64)
+    sp = (group or SingleGroup()).split()
+    rc = _lib.lib().jp2hip_split_psnr_thresholds(
+        keys.ctypes.data_as(POINTER(c_uint64)), cum.ctypes.data_as(POINTER(c_int64)), len(keys),
+        targets.ctypes.data_as(POINTER(c_int64)), len(targets), byref(sp),
+        K.ctypes.data_as(POINTER(c_uint64)))
+    if rc != 0:
+        raise Jp2hipError(f"split psnr thresholds failed ({rc})")
+    return K
+
+
 def band_strips(tif: bytes, layout: Layout, offsets, row0: int, row1: int):
     """The strips a rank reads for image rows [row0, row1), packed back to back.
 
@@ -226,7 +249,8 @@ def encode_split(encoder, d_ptr: int, nbytes: int, layout: Layout, conversion: i
     ``file_len`` and the later ranks' offsets count them), the same
     ``set_tile_part_divisions``, the same ``set_layer_slopes`` (no threshold
     is exchanged then), the same ``set_layer_rates`` (the ranks run one rate
-    loop over the exchanged per-layer sums) and the same ``set_layer_report`` (the ranks' distortion
+    loop over the exchanged per-layer sums), the same ``set_layer_psnr`` (the ranks agree on
+    the thresholds through ``group``) and the same ``set_layer_report`` (the ranks' distortion
     sums travel through ``group``; rank 0's ``layer_report()`` is the image's)."""
     sp = (group or SingleGroup()).split()
     return encoder.encode_device_split(d_ptr, nbytes, layout, conversion, sp, rcp)
